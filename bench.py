@@ -9,8 +9,12 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W        (N > 1:
   * W untimed warmup steps, then EXACTLY K timed steps bracketed by barrier + torch.cuda.synchronize() on both sides,
     MAX over ranks; rank 0 prints ONE JSON line;
   * N > 1 = tensor parallel (column/row shards + RCCL all-reduce over xGMI): total work is fixed -> "scaling": "strong".
+  * a plain run does only that: set-up, W warm-ups, the K timed steps, the outputs (--dump-outputs DIR) and the line.  Everything else
+    below -- the oracle gate, roofline, CPU baseline, run-to-run spread, prefill, the other configurations -- runs with --full only.
+  * --dump-outputs DIR: after the timed steps, the logits of the last timed step (what a caller of the decode step receives; all ranks'
+    vocabulary shards, in rank order) as DIR/logits.npy, float32.  Weights and inputs are seeded: the same arguments give the same inputs.
 
-Extra objects on the JSON line (tier contract 4):
+Extra objects on the JSON line with --full (tier contract 4):
   roofline     : the dominant kernel (the fused EXL3 GEMV, all of its launches in a decode step), bound "hbm":
                  achieved = algorithmic bytes per launch / average launch duration, measured live with HIP events on
                  the launch stream; peak = 8000 GB/s (HBM3E spec, MI355X_MICROARCH.md); traffic = PMC FETCH bytes per
@@ -62,7 +66,39 @@ def parse():
                          "down_proj add into it with integer atomics, 5 launches/layer (fastest measured); glue: deferred-epilogue GEMVs + glue kernels "
                          "(8 launches/layer); tail: sublayer boundaries run inside the GEMV launches (4 launches/layer; the in-kernel cross-workgroup "
                          "hand-off through memory costs more than a launch)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the oracle logits gate, roofline, CPU baseline, run-to-run spread, prefill and the other configurations")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """Write each array as DIR/<name>.npy in float32; an array above its share of 64 MB is replaced by a fixed, seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1) - 4096
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 4, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+
+
+def gathered_logits(model, world):
+    """The logits of the last step as the caller receives them: every rank's vocabulary shard, concatenated in rank order (collective when world > 1)."""
+    mine = model.logits.float().cpu().numpy()
+    if world == 1:
+        return mine
+    import numpy as np
+    import torch.distributed as dist
+    parts = [None] * world
+    dist.all_gather_object(parts, mine)
+    return np.concatenate(parts, axis=-1)
 
 
 def cpu_baseline(shape, K, cb):
@@ -271,6 +307,7 @@ def main():
     from exllamav3_amd.mixtral_path import MIXTRAL_SHAPES, SyntheticEXL3Mixtral
     cb = {"3inst": 0, "mcg": 1, "mul1": 2}[args.codebook]
     is_moe = args.model in MIXTRAL_SHAPES
+    torch.manual_seed(0)            # the input rows (alloc_state) come from the default generator; the weights from the model's own seeded one
     if is_moe:
         # BASELINE config 5: Mixtral layer = attention (tensor-parallel) + sparse-MoE block (expert-parallel over the ranks), 4-bit KV
         shape = MIXTRAL_SHAPES[args.model]
@@ -394,6 +431,41 @@ def main():
     ms_per_step = elapsed * 1e3 / args.steps
     tok_s = args.batch * args.steps / elapsed
     assert torch.isfinite(model.logits.float()).all(), "non-finite logits"
+    if args.dump_outputs:
+        outputs = {"logits": gathered_logits(model, world)}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outputs)
+
+    # the fx pipeline's launches per layer: 6; silu(g) * u inside the down launch: -1; without the attention core the q|k|v epilogue inside o_proj's launch: -1
+    fx_act_in = bool(getattr(model, "fx_act_in_gemv", False) or getattr(model, "fx_gu_atomic", False))
+    fx_qkvm = bool(getattr(model, "qkv_in_oproj", False)) and not args.attention and not getattr(model, "fx_gu_atomic", False) and args.kv_bits == 4 and not is_moe
+    fx_desc = ("fixed-point-residual pipeline (%d launches/layer: o_proj / down_proj add into a 64-bit fixed-point residual with integer atomics, no split-k-reduce / "
+               "residual launches%s%s)" % (6 - int(fx_act_in) - int(fx_qkvm), "; silu(g) * u formed inside the down launch" if fx_act_in else "",
+                                           "; the q|k|v epilogue (RoPE, K / V append) runs inside o_proj's launch" if fx_qkvm else ""))
+    out = None
+    if rank == 0:
+        out = {
+            "metric": ("decode tok/s, Mixtral-8x7B EXL3 %d.0bpw hot path (attention linears + top-2 of 8 experts per layer + RMSNorm + RoPE + KV-quant), bs=%d" % (args.bits, args.batch)) if is_moe else "decode tok/s, %s EXL3 %d.0bpw hot path (all quantized linears + RMSNorm + RoPE + KV-quant), bs=%d" % (
+                {"llama-3.1-8b": "Llama-3.1-8B", "llama-3.2-1b": "Llama-3.2-1B", "llama-3.1-70b": "Llama-3.1-70B"}.get(shape.name, shape.name), args.bits, args.batch),
+            "value": round(tok_s, 2), "unit": "tok/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f16", "data": "synthetic",
+            "config": {"workload": f"{shape.name} EXL3 {args.bits}.0bpw {args.codebook} codebook, decode bs={args.batch}, "
+                                   f"{model.n_layers} layers, {'attention TP=%d + expert-parallel MoE over %d rank(s)' % (world, world) if is_moe else 'TP=%d' % world}, {args.kv_bits}-bit KV append, "
+                                   f"{'hipGraph replay' if graph is not None else 'eager launches'}, { 'glue pipeline + indexed exl3_mgemm MoE block' if is_moe else {'tail': 'tail-epilogue pipeline (4 launches/layer)', 'glue': 'fused glue pipeline (%d launches/layer)' % (7 if (args.batch == 1 and model.act_in_gemv and world == 1) else ((8 if (world == 1 and model.fold_rotate) else 10) if args.batch > 4 else 8)), 'resid': 'resid-in-GEMV pipeline (5 launches/layer: residual add + RMSNorm finished inside the consumer GEMV)' if (args.batch <= 4 and world == 1) else 'fused glue pipeline', 'fx': fx_desc if (args.batch <= model.fx_max_bsz and world == 1) else 'fused glue pipeline', 'unfused': 'one launch per reference op', 'persistent': 'persistent decode step: ONE launch per step (exl3_pstep.hip: 12 streaming + 4 service waves per CU, three decode-ahead units, tagged slab lines, direct residual edges; residual kept in fp32)'}[pipeline] }; "
+                                   f"{'attention core INCLUDED: quant-cache-direct decode attention over a 1000-token context' if args.attention else 'attention core excluded (SURVEY.md 2.1)'}",
+                       "bytes_per_token": shape.decode_bytes_per_token(args.bits), "hbm_roofline_tok_s": round(HBM_PEAK_GBPS * 1e9 / shape.decode_bytes_per_token(args.bits), 1),
+                       "frac_of_hbm_roofline": round(tok_s / args.batch / (HBM_PEAK_GBPS * 1e9 / shape.decode_bytes_per_token(args.bits)), 4),
+                       "parallelism": f"tp{world}", "gemv_variant": args.variant},
+            "persistent_fallback": persistent_fallback,
+        }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        backend.close()
+        return
+
+    # ---- --full: everything beside the headline
     # the pipeline that was just timed, on a pinned one-layer model of the same shape, against the oracle's committed logits (Llama shapes, one rank)
     logits_check = None
     if world == 1 and not is_moe:
@@ -965,30 +1037,9 @@ def main():
     if rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(shape, args.bits, cb)
 
-    # the fx pipeline's launches per layer: 6; silu(g) * u inside the down launch: -1; without the attention core the q|k|v epilogue inside o_proj's launch: -1
-    fx_act_in = bool(getattr(model, "fx_act_in_gemv", False) or getattr(model, "fx_gu_atomic", False))
-    fx_qkvm = bool(getattr(model, "qkv_in_oproj", False)) and not args.attention and not getattr(model, "fx_gu_atomic", False) and args.kv_bits == 4 and not is_moe
-    fx_desc = ("fixed-point-residual pipeline (%d launches/layer: o_proj / down_proj add into a 64-bit fixed-point residual with integer atomics, no split-k-reduce / "
-               "residual launches%s%s)" % (6 - int(fx_act_in) - int(fx_qkvm), "; silu(g) * u formed inside the down launch" if fx_act_in else "",
-                                           "; the q|k|v epilogue (RoPE, K / V append) runs inside o_proj's launch" if fx_qkvm else ""))
     if rank == 0:
-        out = {
-            "metric": ("decode tok/s, Mixtral-8x7B EXL3 %d.0bpw hot path (attention linears + top-2 of 8 experts per layer + RMSNorm + RoPE + KV-quant), bs=%d" % (args.bits, args.batch)) if is_moe else "decode tok/s, %s EXL3 %d.0bpw hot path (all quantized linears + RMSNorm + RoPE + KV-quant), bs=%d" % (
-                {"llama-3.1-8b": "Llama-3.1-8B", "llama-3.2-1b": "Llama-3.2-1B", "llama-3.1-70b": "Llama-3.1-70B"}.get(shape.name, shape.name), args.bits, args.batch),
-            "value": round(tok_s, 2), "unit": "tok/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f16", "data": "synthetic",
-            "config": {"workload": f"{shape.name} EXL3 {args.bits}.0bpw {args.codebook} codebook, decode bs={args.batch}, "
-                                   f"{model.n_layers} layers, {'attention TP=%d + expert-parallel MoE over %d rank(s)' % (world, world) if is_moe else 'TP=%d' % world}, {args.kv_bits}-bit KV append, "
-                                   f"{'hipGraph replay' if graph is not None else 'eager launches'}, { 'glue pipeline + indexed exl3_mgemm MoE block' if is_moe else {'tail': 'tail-epilogue pipeline (4 launches/layer)', 'glue': 'fused glue pipeline (%d launches/layer)' % (7 if (args.batch == 1 and model.act_in_gemv and world == 1) else ((8 if (world == 1 and model.fold_rotate) else 10) if args.batch > 4 else 8)), 'resid': 'resid-in-GEMV pipeline (5 launches/layer: residual add + RMSNorm finished inside the consumer GEMV)' if (args.batch <= 4 and world == 1) else 'fused glue pipeline', 'fx': fx_desc if (args.batch <= model.fx_max_bsz and world == 1) else 'fused glue pipeline', 'unfused': 'one launch per reference op', 'persistent': 'persistent decode step: ONE launch per step (exl3_pstep.hip: 12 streaming + 4 service waves per CU, three decode-ahead units, tagged slab lines, direct residual edges; residual kept in fp32)'}[pipeline] }; "
-                                   f"{'attention core INCLUDED: quant-cache-direct decode attention over a 1000-token context' if args.attention else 'attention core excluded (SURVEY.md 2.1)'}",
-                       "bytes_per_token": shape.decode_bytes_per_token(args.bits), "hbm_roofline_tok_s": round(HBM_PEAK_GBPS * 1e9 / shape.decode_bytes_per_token(args.bits), 1),
-                       "frac_of_hbm_roofline": round(tok_s / args.batch / (HBM_PEAK_GBPS * 1e9 / shape.decode_bytes_per_token(args.bits)), 4),
-                       "parallelism": f"tp{world}", "gemv_variant": args.variant},
-            "repeat_ms_per_step": repeat_ms, "allreduce": allreduce, "persistent_fallback": persistent_fallback,
-            "logits_check": logits_check,
-            "roofline": roofline, "cpu_baseline": cpu, "prefill": prefill, "other_configs": extra,
-        }
+        out.update({"repeat_ms_per_step": repeat_ms, "allreduce": allreduce, "logits_check": logits_check,
+                    "roofline": roofline, "cpu_baseline": cpu, "prefill": prefill, "other_configs": extra})
         print(json.dumps(out), flush=True)
     backend.close()
 

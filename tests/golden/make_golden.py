@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """
-Generate tests/golden/ref_python.npz by IMPORTING the reference's own Python (read-only at
+Generate tests/golden/ref_python_part*.npz by IMPORTING the reference's own Python (read-only at
 /root/reference) in the build container and running its pure-torch CPU code on seeded inputs.
 
 The reference's native extension cannot be built here (CUDA/PTX only), so
@@ -10,14 +10,14 @@ the stub returns a caller-supplied W_hat, so what is pinned is the reference's C
 (Hadamard side/order/scale, suh/svh placement), not our decode.
 
 Run:  python tests/golden/make_golden.py        (only possible where /root/reference exists)
-Nothing under tests/, bench.py or smoke() reads /root/reference at run time; they read the .npz.
+Nothing under tests/, bench.py or smoke() reads the reference tree at run time; they read the .npz parts.
 """
 import sys, types, importlib, os, math
 import numpy as np
 import torch
 
 REF = "/root/reference/exllamav3"
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_python.npz")
+OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ref_python")          # written as ref_python_part*.npz (npz_parts.py)
 
 
 def fake_pkg(name, path):
@@ -201,8 +201,8 @@ def main():
         o_ = attn_t._torch_bighead_fallback(q, kn, vn, kc, vc, bt.long(), cl, causal=True, softmax_scale=hd ** -0.5)
         out[f"attn_{tag}_out"] = o_.float().numpy()
 
-    np.savez_compressed(OUT, **out)
-    print("wrote", OUT, {k: getattr(v, "shape", None) for k, v in out.items()})
+    from npz_parts import save_parts
+    print("wrote", save_parts(OUT, out), {k: getattr(v, "shape", None) for k, v in out.items()})
 
 
 if __name__ == "__main__":

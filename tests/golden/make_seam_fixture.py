@@ -1,4 +1,4 @@
-"""Generates tests/golden/ref_seam_calls.npz (run on a box that has /root/reference; the GPU box does not):
+"""Generates tests/golden/ref_seam_calls_part*.npz (run where the reference sources are present; the GPU machines lack them):
 
     PYTHONPATH=exllamav3_amd/stub:.:/root/reference python tests/golden/make_seam_fixture.py
 
@@ -124,10 +124,11 @@ def main():
             return (qo, ko)[which], (rq, rk)[which].astype(np.float32), 3e-3
         add(f"rope_{'qk'[which]}", build_rope)
 
-    out = os.path.join(ROOT, "tests", "golden", "ref_seam_calls.npz")
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from npz_parts import save_parts
     arrays["meta"] = np.frombuffer(json.dumps(cases).encode(), dtype=np.uint8)
-    np.savez_compressed(out, **arrays)
-    nbytes = os.path.getsize(out)
+    out = save_parts(os.path.join(ROOT, "tests", "golden", "ref_seam_calls"), arrays)
+    nbytes = sum(os.path.getsize(f) for f in out)
     print(f"wrote {out}: {len(cases)} cases, {sum(len(c['calls']) for c in cases.values())} recorded calls, {nbytes / 1e6:.2f} MB")
     for name, c in cases.items():
         print(f"  {name}: " + " -> ".join(call["op"] for call in c["calls"]))

@@ -19,7 +19,7 @@ def _line(out: str) -> dict:
 
 
 def test_bench_single_process_line(dev):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "2", "--steps", "3", "--warmup", "1", "--no-prefill", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "2", "--steps", "3", "--warmup", "1", "--no-prefill", "--no-cpu", "--full"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _line(r.stdout)
@@ -29,14 +29,34 @@ def test_bench_single_process_line(dev):
     # the default step of this configuration is the persistent one: ONE launch per step is the dominant kernel, the launch-per-op GEMV table rides along
     assert rf["launches_per_step"] == 1 and "exl3_pstep_kernel" in rf["kernel"] and len(rf["launch_per_op_gemv"]["per_launch"]) == 5
     assert d["logits_check"]["step"] == "decode_step_persistent" and not d["logits_check"]["edge_timeout"]
-    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "2", "--steps", "3", "--warmup", "1", "--no-prefill", "--no-cpu", "--pipeline", "fx"],
+    r2 = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "2", "--steps", "3", "--warmup", "1", "--no-prefill", "--no-cpu", "--pipeline", "fx", "--full"],
                         capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r2.returncode == 0, r2.stderr[-2000:]
     d2 = _line(r2.stdout)
     assert d2["roofline"]["launches_per_step"] > 1 and len(d2["roofline"]["per_launch"]) == 5 and d2["roofline"]["fit"]["const_us"] > 0
 
 
-def test_bench_two_ranks_control_flow(dev):
+def test_bench_plain_line_and_dumped_outputs(dev, tmp_path):
+    """A plain run (no --full) prints the headline only; --dump-outputs writes the last timed step's logits, and the same arguments give the same
+    inputs, so two runs agree."""
+    import numpy as np
+    got = []
+    for i in range(2):
+        d_out = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--layers", "2", "--steps", "4", "--warmup", "1", "--dump-outputs", str(d_out)],
+                           capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _line(r.stdout)
+        assert {"metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype"} <= set(d) and d["steps"] == 4 and d["warmup"] == 1
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and not ({"roofline", "cpu_baseline", "prefill", "other_configs", "logits_check"} & set(d))
+        lg = np.load(d_out / "logits.npy")
+        assert lg.dtype == np.float32 and lg.shape == (1, 128256) and np.isfinite(lg).all()
+        got.append(lg)
+    rms = float(np.sqrt((got[0].astype(np.float64) ** 2).mean()))
+    assert rms > 0 and float(np.abs(got[0] - got[1]).max()) <= 1e-3 * rms
+
+
+def test_bench_two_ranks_control_flow(dev, tmp_path):
     """`--gpus 2` as launched by the driver (torch.distributed.run, one rank per process).  This box has one GPU, so the test hook
     EXL3_HIP_TP_BACKEND=gloo lets both ranks share it (RCCL refuses that) -- the collectives are gloo's, everything else is the
     multi-rank path of bench.py: per-rank shards, barriers, max-over-ranks timing, rank 0 printing the one line."""
@@ -44,7 +64,7 @@ def test_bench_two_ranks_control_flow(dev):
     env = dict(os.environ, EXL3_HIP_TP_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--layers", "2", "--steps", "2", "--warmup", "1",
-                        "--no-graph", "--prefill-tokens", "512"], capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)
+                        "--no-graph", "--prefill-tokens", "512", "--full", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _line(r.stdout)
     assert KEYS <= set(d) and d["n_gpus"] == 2 and d["value"] > 0 and d["config"]["parallelism"] == "tp2" and d["cpu_baseline"] is None
@@ -56,6 +76,10 @@ def test_bench_two_ranks_control_flow(dev):
     pf = d["prefill"]
     assert pf["n_gpus"] == 2 and pf["value"] > 0 and pf["allreduce"]["per_chunk"] == 4 and pf["allreduce"]["prefill_ms"] > 0
     assert pf["allreduce"]["message_bytes"] == 512 * 4096 * 4
+    # the dumped logits are both ranks' vocabulary shards, gathered in rank order
+    import numpy as np
+    lg = np.load(tmp_path / "logits.npy")
+    assert lg.dtype == np.float32 and lg.shape == (1, 128256) and np.isfinite(lg).all()
 
 
 @pytest.mark.parametrize("name,K,cb,bsz,pipeline", [("llama-3.1-8b", 4, 2, 1, "fx"), ("llama-3.1-8b", 4, 0, 1, "fx"), ("llama-3.1-8b", 4, 2, 16, "fx"),

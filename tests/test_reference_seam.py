@@ -1,4 +1,4 @@
-"""The drop-in boundary demonstrated with the reference's OWN Python (CPU, needs /root/reference; skipped elsewhere): the CPython stub
+"""The drop-in boundary demonstrated with the reference's OWN Python (CPU, needs the reference tree; skipped elsewhere, but for the name check, which reads a record there): the CPython stub
 exllamav3_amd/stub/exllamav3_ext*.so is found by the import seam of exllamav3/ext.py:20-30 (find_spec + EXTENSION_SUFFIXES), the whole
 reference package imports over it unchanged, and every `ext.<name>` the reference's hot-path modules use resolves on it."""
 import ast
@@ -51,13 +51,26 @@ def test_reference_package_imports_over_the_stub():
     assert r.returncode == 0 and "SEAM_OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
 
 
-@needs_ref
+# the `ext.<name>`s of HOT_MODULES, recorded (python tests/test_reference_seam.py writes it where the reference tree is present)
+NAMES_RECORD = os.path.join(ROOT, "tests", "golden", "ref_hot_path_ext_names.json")
+
+
+def _hot_path_names():
+    return {m: sorted(_ext_names(os.path.join(REF, "exllamav3", m))) for m in HOT_MODULES}
+
+
 def test_every_hot_path_ext_name_resolves():
+    """Against the reference tree where it is present (and then the record must agree with it), else against the record."""
+    import json
     sys.path.insert(0, ROOT)
     from exllamav3_amd import ext
+    recorded = json.load(open(NAMES_RECORD))
+    if os.path.isdir(os.path.join(REF, "exllamav3")):
+        assert _hot_path_names() == recorded, "tests/golden/ref_hot_path_ext_names.json is stale: run python tests/test_reference_seam.py"
+    assert sorted(recorded) == sorted(HOT_MODULES)
     missing = {}
     for m in HOT_MODULES:
-        names = _ext_names(os.path.join(REF, "exllamav3", m)) - OUTSIDE
+        names = set(recorded[m]) - OUTSIDE
         miss = sorted(n for n in names if not hasattr(ext, n))
         if miss:
             missing[m] = miss
@@ -87,3 +100,9 @@ def test_loader_and_writer_pinned_against_the_reference_reader_and_naming_code()
     assert r.returncode == 0 and "REFERENCE_LOADER_OK" in r.stdout, (r.stdout + r.stderr)[-3000:]
     for tag in ("A_OK 45", "B_OK 4", "C_OK", "D_OK"):
         assert tag in r.stdout
+
+
+if __name__ == "__main__":
+    import json
+    json.dump(_hot_path_names(), open(NAMES_RECORD, "w"), indent=1)
+    print("wrote", NAMES_RECORD)

@@ -5,6 +5,6 @@ BASE=$1; shift
 for rep in 1 2 3; do
   for lib in "$BASE" ""; do
     if [ -n "$lib" ]; then export EXL3_HIP_LIB=$lib; else unset EXL3_HIP_LIB; fi
-    timeout 300 python bench.py --no-extra --no-cpu "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('${lib:-new}', d['value'], d['ms_per_step'], d.get('repeat_ms_per_step'))"
+    timeout 300 python bench.py --no-extra --no-cpu --full "$@" 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('${lib:-new}', d['value'], d['ms_per_step'], d.get('repeat_ms_per_step'))"
   done
 done

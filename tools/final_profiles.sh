@@ -11,9 +11,9 @@ run() { # name, bench args...
 run bs1 --no-prefill --steps 20
 run bs16 --batch 16 --no-prefill --steps 20
 run bs1_attention --attention --no-prefill --steps 20
-run mixtral --model mixtral-8x7b --steps 10
-run prefill --steps 5
-run prefill_attn --attention --steps 5
+run mixtral --model mixtral-8x7b --steps 10 --full
+run prefill --steps 5 --full
+run prefill_attn --attention --steps 5 --full
 # PMC pass: eager launches (one dispatch record per kernel), FETCH_SIZE in KiB, x2 on gfx950 for wide coalesced reads (MI355X_MICROARCH.md)
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc -o out --output-format csv -- python $R/bench.py --no-extra --no-cpu --no-prefill --steps 3 --warmup 1 --no-graph > $O/pmc.log 2>&1
 python - <<PY
@@ -40,5 +40,5 @@ else:
     print("no PMC rows", len(rows), [r for r in rows[:2]])
 PY
 rm -rf $O/pmc
-timeout 300 python $R/bench.py > $O/${TAG}_bench_default.json 2> $O/default.err
+timeout 600 python $R/bench.py --full > $O/${TAG}_bench_default.json 2> $O/default.err
 ls $O; for f in $O/${TAG}_bench_*_under_rocprof.json $O/${TAG}_bench_default.json; do echo $f; grep "^{" $f | cut -c1-200; done

@@ -13,10 +13,10 @@ try:
 except Exception as e: print('$1', 'FAILED', e)
 "; }
 for rep in 1 2; do
-  EXL3_HIP_GEMV_GEN4=0 timeout 300 python bench.py --no-extra --no-cpu --no-prefill 2>$O/err_gen2.txt | line gen2
-  EXL3_HIP_GEMV_GEN4=1 timeout 300 python bench.py --no-extra --no-cpu --no-prefill 2>$O/err_g4act.txt | line gen4_act_in_gemv
-  EXL3_HIP_GEMV_GEN4=1 EXL3_HIP_ACT_IN_GEMV=0 timeout 300 python bench.py --no-extra --no-cpu --no-prefill 2>$O/err_g4glue.txt | line gen4_glue_act
-  EXL3_HIP_GEMV_GEN4=1 EXL3_HIP_ROTATE_ABOVE=0 timeout 300 python bench.py --no-extra --no-cpu --no-prefill 2>$O/err_g4rot.txt | line gen4_rotated_pipeline
+  EXL3_HIP_GEMV_GEN4=0 timeout 300 python bench.py --no-extra --no-cpu --no-prefill --full 2>$O/err_gen2.txt | line gen2
+  EXL3_HIP_GEMV_GEN4=1 timeout 300 python bench.py --no-extra --no-cpu --no-prefill --full 2>$O/err_g4act.txt | line gen4_act_in_gemv
+  EXL3_HIP_GEMV_GEN4=1 EXL3_HIP_ACT_IN_GEMV=0 timeout 300 python bench.py --no-extra --no-cpu --no-prefill --full 2>$O/err_g4glue.txt | line gen4_glue_act
+  EXL3_HIP_GEMV_GEN4=1 EXL3_HIP_ROTATE_ABOVE=0 timeout 300 python bench.py --no-extra --no-cpu --no-prefill --full 2>$O/err_g4rot.txt | line gen4_rotated_pipeline
 done 2>&1 | tee $O/ab.txt
 # kernel-level view of the two generation-4 pipelines
 cd /tmp && export TMPDIR=/tmp

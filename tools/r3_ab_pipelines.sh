@@ -6,7 +6,7 @@ REPS=${REPS:-3}
 for rep in $(seq $REPS); do
   for cfg in "$@"; do
     name=${cfg%%:*}; rest=${cfg#*:}; envs=${rest%%:*}; args=${rest#*:}
-    env $envs timeout 300 python bench.py --no-extra --no-cpu --no-prefill $args 2>$O/err_$name.txt | python -c "
+    env $envs timeout 300 python bench.py --no-extra --no-cpu --no-prefill --full $args 2>$O/err_$name.txt | python -c "
 import sys,json
 try:
     d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); r=d.get('roofline') or {}

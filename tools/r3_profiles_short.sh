@@ -7,6 +7,6 @@ run() { n=$1; shift
   cp $O/$n/out_kernel_stats.csv $O/${TAG}_bench_${n}_kernel_stats.csv 2>/dev/null; rm -rf $O/$n; }
 run bs1 --no-prefill --steps 20
 run bs16 --batch 16 --no-prefill --steps 20
-run mixtral --model mixtral-8x7b --steps 10
-run prefill --steps 5
+run mixtral --model mixtral-8x7b --steps 10 --full
+run prefill --steps 5 --full
 ls $O | grep r03 | head -20

@@ -20,7 +20,7 @@ run 1b_persistent --model llama-3.2-1b --no-prefill --steps 20
 run 1b_launch_per_op --model llama-3.2-1b --pipeline fx --no-prefill --steps 20
 run bs1_attention --attention --no-prefill --steps 20
 run bs1_attention_launch_per_op --attention --pipeline fx --no-prefill --steps 20
-run prefill --steps 5
+run prefill --steps 5 --full
 # PMC passes: eager launches (one dispatch record per kernel), FETCH_SIZE in KiB, x2 on gfx950 for wide coalesced reads (MI355X_MICROARCH.md).  One pass per pipeline:
 # the launch-per-op GEMV launches, the persistent step's ONE kernel (8B and 1B)
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc -o out --output-format csv -- python $R/bench.py --no-extra --no-cpu --no-prefill --steps 3 --warmup 1 --no-graph --pipeline fx > $O/pmc.log 2>&1
@@ -64,5 +64,5 @@ out["persistent_step"] = ps
 json.dump(out, open("$O/traffic.json", "w"), indent=1)
 PY
 rm -rf $O/pmc $O/pmc_p8 $O/pmc_p1
-cd $R; timeout 400 python bench.py > $O/${TAG}_bench_final.json 2> $O/final.err; tail -c 300 $O/final.err
+cd $R; timeout 400 python bench.py --full > $O/${TAG}_bench_final.json 2> $O/final.err; tail -c 300 $O/final.err
 ls $O; for f in $O/${TAG}_bench_*_under_rocprof.json $O/${TAG}_bench_final.json; do echo $f; grep "^{" $f | cut -c1-260; done

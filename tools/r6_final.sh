@@ -35,7 +35,7 @@ run bs1_launch_per_op --pipeline fx --no-prefill --steps 20
 run 1b_persistent --model llama-3.2-1b --no-prefill --steps 50
 run bs1_attention --attention --no-prefill --steps 20
 run bs1_3inst --codebook 3inst --no-prefill --steps 20
-run prefill --steps 5
+run prefill --steps 5 --full
 # PMC passes: eager launches (one dispatch record per kernel), FETCH_SIZE in KiB, x2 on gfx950 for wide coalesced reads (MI355X_MICROARCH.md)
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc -o out --output-format csv -- python $R/bench.py --no-extra --no-cpu --no-prefill --steps 3 --warmup 1 --no-graph --pipeline fx > $O/pmc.log 2>&1
 timeout 300 rocprofv3 --pmc FETCH_SIZE -d $O/pmc_p8 -o out --output-format csv -- python $R/bench.py --no-extra --no-cpu --no-prefill --steps 3 --warmup 1 --no-graph > $O/pmc_p8.log 2>&1
@@ -88,7 +88,7 @@ H_SPIN_LIMIT=20000 timeout 90 tools/bin/pstep_harness 8b 0 1 "3" $O/s_8b.bin 2>&
 python3 tools/pstep_stamps.py $O/s_1b.bin 16 $O/${TAG}_stamps_1b.json > $O/${TAG}_stamps_1b.txt; python3 tools/pstep_stamps.py $O/s_8b.bin 32 $O/${TAG}_stamps_8b.json > $O/${TAG}_stamps_8b.txt
 python3 tools/pstep_stragglers.py $O/s_8b.bin 32 > $O/${TAG}_stragglers_8b.txt; rm -f $O/s_1b.bin $O/s_8b.bin
 for r in 1 2 3; do for m in 8b 1b; do H_SPIN_LIMIT=20000 timeout 120 tools/bin/pstep_harness $m 0 2 "3" 2>/dev/null | grep -o '"best".*' | cut -c1-220; done; done > $O/${TAG}_harness_final.txt
-timeout 600 python bench.py > $O/${TAG}_bench_final.json 2> $O/final.err; tail -c 300 $O/final.err
+timeout 600 python bench.py --full > $O/${TAG}_bench_final.json 2> $O/final.err; tail -c 300 $O/final.err
 timeout 300 python bench.py --no-extra --no-cpu --no-prefill --steps 200 --warmup 20 > $O/${TAG}_bench_steps200.json 2>> $O/final.err
 STEP=persistent timeout 300 python tools/bench_decode_ctx.py > $O/${TAG}_decode_ctx.txt 2>&1
 ls $O; for f in $O/${TAG}_bench_*_under_rocprof.json $O/${TAG}_bench_final.json $O/${TAG}_bench_steps200.json; do echo $f; grep "^{" $f | cut -c1-200; done
