@@ -100,6 +100,8 @@ def _declare(l):
     sig("exl3_unpack_trellis", vp, vp, i32, i32, i32, vp)
     sig("exl3_pack_signs", vp, vp, i64, vp)
     sig("exl3_decode", vp, vp, i64, i32, i32, vp)
+    sig("exl3_quantize_tiles_workspace", i32, ctypes.POINTER(i64))
+    sig("exl3_quantize_tiles", vp, vp, vp, i64, vp, i64, i32, i32, vp)
     sig("exl3_reconstruct", vp, vp, i32, i32, i32, i32, i64, i64, vp)
     sig("exl3_reconstruct_had", vp, vp, vp, vp, i32, i32, i32, i32, i64, i64, vp)
     sig("exl3_had_r_128", vp, vp, vp, vp, f32, i32, i32, i32, vp)

@@ -155,6 +155,98 @@ def decode(idx: torch.Tensor, out: torch.Tensor, mcg: bool, mul1: bool):
     _check(_lib.lib().exl3_decode(_p(idx), _p(out), idx.numel(), int(out.dtype == torch.float), _cb(mcg, mul1), _stream(idx)))
 
 
+def quantize_tiles(input_tiles: torch.Tensor, output_tiles: torch.Tensor, output_indices: torch.Tensor, temp_costs: torch.Tensor,
+                   temp_edges: torch.Tensor, K: int, mcg: bool, mul1: bool):
+    """quant/quantize.cu:27-87: tail-biting Viterbi encoding of (n, 256) fp32 tiles into int16 trellis states (output_indices) and their
+    decoded values (output_tiles, fp32).  At most temp_costs.size(0) tiles per launch; temp_edges is the raw back-pointer workspace of those
+    tiles (exl3_quantize_tiles_workspace(K) bytes each, at most one (256, E) int16 slot); temp_costs only sizes the batch (the costs live in LDS)."""
+    _req(input_tiles.dim() == 2, "input_tiles must have 2 dimensions")
+    _req(input_tiles.shape[1] == 256, "input_tiles dim 1 must be 256")
+    _req(tuple(input_tiles.shape) == tuple(output_indices.shape), "input_tiles and output_indices must have the same shape")
+    _req(tuple(input_tiles.shape) == tuple(output_tiles.shape), "input_tiles and output_tiles must have the same shape")
+    _req(input_tiles.dtype == torch.float, "input_tiles must be float32")
+    _req(output_tiles.dtype == torch.float, "output_tiles must be float32")
+    _req(output_indices.dtype == torch.short, "output_indices must be int16")
+    _req(1 <= int(K) <= 8, "quantize_tiles K must be in range 1..8")
+    K = int(K)
+    edges = 65536 >> K
+    num_tiles = input_tiles.shape[0]
+    if num_tiles == 0:
+        return
+    _req(temp_costs.dtype == torch.half and temp_costs.dim() == 3 and temp_costs.shape[1] == 2 and temp_costs.shape[2] == edges,
+         "temp_costs must be float16 (b, 2, 65536 >> K)")
+    _req(temp_edges.dtype == torch.short and temp_edges.dim() == 3 and temp_edges.shape[1] == 256 and temp_edges.shape[2] == edges,
+         "temp_edges must be int16 (b, 256, 65536 >> K)")
+    _req(input_tiles.is_contiguous() and output_tiles.is_contiguous() and output_indices.is_contiguous() and temp_edges.is_contiguous(),
+         "quantize_tiles: tensors must be contiguous")
+    for t in (output_tiles, output_indices, temp_costs, temp_edges):
+        _req(t.device == input_tiles.device, "quantize_tiles: tensors must be on one device")
+    _dev(input_tiles)
+    per_tile = ctypes.c_int64(0)
+    _check(_lib.lib().exl3_quantize_tiles_workspace(K, ctypes.byref(per_tile)))
+    max_batch = min(temp_costs.shape[0], temp_edges.numel() * 2 // per_tile.value)
+    _req(max_batch >= 1, "quantize_tiles: temp buffers must hold at least one tile")
+    _check(_lib.lib().exl3_quantize_tiles(_p(input_tiles), _p(output_tiles), _p(output_indices), num_tiles, _p(temp_edges), max_batch,
+                                          K, _cb(mcg, mul1), _stream(input_tiles)))
+
+
+def quantize_tiles_workspace_bytes(K: int) -> int:
+    """Back-pointer workspace of one tile of quantize_tiles (bytes)."""
+    per_tile = ctypes.c_int64(0)
+    _check(_lib.lib().exl3_quantize_tiles_workspace(int(K), ctypes.byref(per_tile)))
+    return per_tile.value
+
+
+def _is_quadratic_residue(a: int, p: int) -> bool:
+    # Euler's criterion, as hadamard.cpp:28-31
+    return pow(a % p, (p - 1) // 2, p) == 1
+
+
+def had_paley(h: torch.Tensor):
+    """hadamard.cpp:35-64 (host code): Paley construction I of order n = p + 1 into a CPU fp16 (n, n) tensor, in place."""
+    _req(h.dtype == torch.half, "had_paley: h must be float16")
+    _req(h.dim() == 2 and h.shape[0] == h.shape[1], "had_paley: h must be square")
+    _req(h.is_contiguous() and h.device.type == "cpu", "had_paley: h must be a contiguous CPU tensor")
+    n = h.shape[0]
+    p = n - 1
+    m = torch.empty((n, n), dtype=torch.half)
+    m[0, :] = 1
+    m[1:, 0] = -1
+    if p > 0:
+        qr = torch.tensor([1.0 if _is_quadratic_residue(r, p) else -1.0 for r in range(p)], dtype=torch.half)
+        i = torch.arange(p)
+        r = (i[:, None] - i[None, :]) % p
+        blk = qr[r]
+        blk.fill_diagonal_(1)
+        m[1:, 1:] = blk
+    h.copy_(m)
+
+
+def had_paley2(h: torch.Tensor):
+    """hadamard.cpp:68-110 (host code): Paley construction II of order n = 2 (p + 1) into a CPU fp16 (n, n) tensor, in place."""
+    _req(h.dtype == torch.half, "had_paley2: h must be float16")
+    _req(h.dim() == 2 and h.shape[0] == h.shape[1], "had_paley2: h must be square")
+    _req(h.is_contiguous() and h.device.type == "cpu", "had_paley2: h must be a contiguous CPU tensor")
+    n = h.shape[0]
+    q = n // 2
+    p = q - 1
+    i = torch.arange(q)
+    if p > 0:
+        qr = torch.tensor([_is_quadratic_residue(r, p) for r in range(p)], dtype=torch.bool)
+        pos = qr[(i[:, None] - i[None, :]) % p]
+    else:
+        pos = torch.zeros((q, q), dtype=torch.bool)
+    pos |= (i[:, None] == 0) | (i[None, :] == 0)
+    diag = i[:, None] == i[None, :]
+    # 2x2 blocks: diagonal [[1, -1], [-1, -1]], positive [[1, 1], [1, -1]], negative [[-1, -1], [-1, 1]]
+    a = torch.where(diag, 1.0, torch.where(pos, 1.0, -1.0))
+    b = torch.where(diag, -1.0, torch.where(pos, 1.0, -1.0))
+    c = torch.where(diag, -1.0, torch.where(pos, 1.0, -1.0))
+    d = torch.where(diag, -1.0, torch.where(pos, -1.0, 1.0))
+    m = torch.stack([torch.stack([a, b], -1), torch.stack([c, d], -1)], 1).reshape(n, n)
+    h.copy_(m.to(torch.half))
+
+
 def _check_packed(unpacked, packed, K):
     _req(packed.dim() == 3 and packed.dtype == torch.int16, "packed must be a 3-D int16 tensor")
     _req(packed.shape[2] == 256 * K // 16, "packed dim 2 must be 16*K")

@@ -91,6 +91,16 @@ int exl3_reconstruct_had_multi_t_interleaved(void* out, int64_t ld_out, const vo
 int exl3_had_r_128(const void* in, void* out, const void* pre_scale, const void* post_scale, float scale,
                    int rows, int cols, int fp32, void* stream);
 
+/* ---- trellis encoder (conversion)    quant/quantize.cu:27-87, quant/quantize_tiles_kernel.cuh ------------------------------------------
+ * quantize_tiles(input_tiles, output_tiles, output_indices, temp_costs, temp_edges, K, mcg, mul1): the tail-biting Viterbi search of the EXL3
+ * converter.  input fp32 [num_tiles][256] (tile elements in stream order), out: indices u16 [num_tiles][256] (16-bit trellis states, tail-biting:
+ * idx[0] >> K == idx[255] & ((65536 >> K) - 1)) and output fp32 [num_tiles][256] = decode(indices).  Indices are bit-identical to the reference
+ * encoder's.  workspace: device memory of at least max_batch * exl3_quantize_tiles_workspace(K) bytes (the back-pointers of max_batch tiles);
+ * tiles are encoded in launches of at most max_batch; the result does not depend on max_batch.  Inputs must be finite. */
+int exl3_quantize_tiles_workspace(int K, int64_t* bytes_per_tile);
+int exl3_quantize_tiles(const void* input, void* output, void* indices, int64_t num_tiles, void* workspace, int64_t max_batch,
+                        int K, int cb, void* stream);
+
 /* ---- quantized GEMM / GEMV --------------------------------------------------------------------- */
 
 /* exl3_gemm(A, B, C, suh, A_had, svh, force_shape_idx, mcg, mul1, force_num_sms)   quant/exl3_gemm.cuh:21-33
