@@ -226,6 +226,10 @@ def _declare(l):
     sig("exl3_fx_zero_next", vp, i64)
     sig("exl3_fx_add", vp, vp, vp, i32, vp, i32, i32, vp)
     sig("exl3_ar_reduce_fx", vp, vp, vp, i32, vp, vp, i32, i32, vp)
+    # device-side token generation (exl3_sampler.hip)
+    sig("exl3_sample_workspace", i32, ctypes.POINTER(i64))
+    sig("exl3_sample", vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, u32, u32, vp, i32, vp, i64, vp, vp, vp, vp)
+    sig("exl3_gen_feed", vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp)
     sig("exl3_set_gemv_variant", i32)
     sig("exl3_set_gemv_max_waves", i32)
     sig("exl3_set_gemv_gen4", i32)

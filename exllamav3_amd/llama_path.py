@@ -244,6 +244,8 @@ class SyntheticEXL3Llama:
             t[f"model.layers.{i}.post_attention_layernorm.weight"] = L["norm2"].cpu()
         t["model.norm.weight"] = self.final_norm.cpu()
         put("lm_head", self.lm_head)
+        if getattr(self, "_embed", None) is not None:
+            t["model.embed_tokens.weight"] = self._embed.cpu()
         save_file({k: v.contiguous() for k, v in t.items()}, os.path.join(directory, "model.safetensors"))
         s = self.shape
         cfg = {"architectures": ["LlamaForCausalLM"], "hidden_size": s.hidden, "intermediate_size": s.inter, "num_hidden_layers": self.n_layers,
@@ -313,10 +315,15 @@ class SyntheticEXL3Llama:
         self.inv_freq = rope_inv_freq(hd, shape.rope_theta, cfg.get("rope_scaling")).to(self.device)
         self.eps = float(cfg.get("rms_norm_eps", 1e-5))
         self.page, self.max_ctx, self._state_bsz = 256, max_ctx, None
+        self._embed_source = stc                            # model.embed_tokens.weight is read on the first embed_table() call
         return self
 
     # ---- state ---------------------------------------------------------------------------------------
     def alloc_state(self, bsz: int, pos: int = 1000):
+        self._alloc_state(bsz, pos, None)
+
+    def _alloc_state(self, bsz: int, pos: int, x):
+        """alloc_state's buffers; x = the input rows (None: alloc_state's random rows, drawn where it always drew them)."""
         dev, s = self.device, self.shape
         hd = s.head_dim
         kv_dim = self.hkv * hd
@@ -331,7 +338,9 @@ class SyntheticEXL3Llama:
         self.vcache = [(torch.zeros((n_pages, self.page, G * self.kv_bits), dtype=torch.int32, device=dev),
                         torch.zeros((n_pages, self.page, G), dtype=torch.half, device=dev)) for _ in range(self.n_layers)]
         f16, f32 = torch.half, torch.float
-        if getattr(self, "_host_rng", None) is not None:
+        if x is not None:
+            self.x = x
+        elif getattr(self, "_host_rng", None) is not None:
             import numpy as np
             self.x = torch.from_numpy(self._host_rng.standard_normal((bsz, s.hidden)).astype(np.float16)).to(dev)
         else:
@@ -959,6 +968,130 @@ class SyntheticEXL3Llama:
         """decode_step_persistent where it applies and is the faster step (see `persistent`), else decode_step_fx."""
         use = self.persistent if self.persistent is not None else True
         return self.decode_step_persistent() if (use and self.persistent_applies()) else self.decode_step_fx()
+
+    # ---- token generation: embedding table, device-side sampler + token feed, generate() ------------------------------------------------------------
+    #: seed of a synthetic model's embedding table (its own generator: neither the host PCG64 stream of host_seed nor the device generator of `seed` is advanced)
+    embed_seed = 20261016
+
+    def embed_table(self) -> torch.Tensor:
+        """fp16 [vocab, hidden] embedding table, created on the first call: `model.embed_tokens.weight` of the checkpoint the model was loaded from, else
+        seeded random rows of unit RMS (what alloc_state feeds the step).  save_checkpoint writes it when present."""
+        if getattr(self, "_embed", None) is None:
+            s = self.shape
+            src = getattr(self, "_embed_source", None)
+            if src is not None:
+                if not src.has_tensor("model.embed_tokens.weight"):
+                    raise NotImplementedError("the checkpoint has no model.embed_tokens.weight (tied embeddings are not on this path)")
+                self._embed = src.get_tensor("model.embed_tokens.weight", self.device).half().contiguous()
+            else:
+                g = torch.Generator(device=self.device)
+                g.manual_seed(self.embed_seed)
+                self._embed = torch.randn((s.vocab, s.hidden), device=self.device, generator=g, dtype=torch.float).half()
+            assert self._embed.shape[0] >= s.vocab and self._embed.shape[1] == s.hidden, "embedding table does not match the model's shape"
+        return self._embed
+
+    def alloc_gen_state(self, bsz: int, max_new: int, prompt):
+        """alloc_state for a generation from an EMPTY cache: positions start at 0 and everything alloc_state sizes by `pos` (the split-attention workspace, the
+        max_len argument of the launch-per-op attention) is sized by max_ctx.  prompt: token ids [bsz, P] (P >= 1, one length for all rows).  The first prompt
+        token reaches the step's input row through the same entry as every later token (sampling.gen_feed, step word -1 -> 0)."""
+        from types import SimpleNamespace
+        from . import sampling
+        dev = self.device
+        prompt = torch.as_tensor(prompt, dtype=torch.long)
+        assert prompt.dim() == 2 and prompt.shape[0] == bsz and prompt.shape[1] >= 1, "prompt must be [bsz, P] with P >= 1"
+        assert 1 <= bsz <= sampling.MAX_ROWS, "the sampler takes 1..16 rows"
+        P = prompt.shape[1]
+        assert max_new >= 0 and P + max_new <= self.max_ctx, "prompt + new tokens exceed max_ctx"
+        assert int(prompt.min()) >= 0 and int(prompt.max()) < self.shape.vocab, "prompt token outside the vocabulary"
+        embed = self.embed_table()
+        self._alloc_state(bsz, self.max_ctx - 1, torch.zeros((bsz, self.shape.hidden), dtype=torch.half, device=dev))
+        total = max(P - 1 + max_new, 1)
+        self.gen = SimpleNamespace(
+            P=P, total=P - 1 + max_new, embed=embed, forced=prompt.to(torch.int32).to(dev).contiguous(),
+            tokens_out=torch.empty((bsz, total), dtype=torch.int32, device=dev), sampled=torch.empty((bsz,), dtype=torch.int32, device=dev),
+            invalid=torch.empty((bsz,), dtype=torch.int32, device=dev), step=torch.empty((1,), dtype=torch.int64, device=dev),
+            ws=sampling.workspace(bsz, dev))
+        self._gen_prime()
+        return self.gen
+
+    def _gen_prime(self):
+        """(Re)starts the generation state: counters one step before the first token, then the priming feed (forced[:, 0] -> x0, counters and step word + 1)."""
+        from . import sampling
+        gs = self.gen
+        self.positions.fill_(-1); self.cache_seqlens.fill_(-1); self.attn_lens.fill_(0)
+        gs.step.fill_(-1); gs.invalid.zero_(); gs.tokens_out.fill_(-1); gs.sampled.fill_(-1)
+        sampling.gen_feed(None, gs.forced, gs.embed, self.x0, None, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step, vocab=self.shape.vocab)
+
+    def gen_step(self, ka):
+        """The loop body of generate(): decode step, sampler, token feed -- kernel launches only (graph-capturable)."""
+        from . import sampling
+        gs = self.gen
+        logits = self.decode_step_auto()
+        sampling.sample(logits, ka, gs.step, size=self.shape.vocab, out=gs.sampled, ws=gs.ws)
+        sampling.gen_feed(gs.sampled, gs.forced, gs.embed, self.x0, gs.tokens_out, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step,
+                          vocab=self.shape.vocab)
+
+    def generate(self, prompt_ids, max_new_tokens: int, settings=None, eos_token_id: int | None = None) -> torch.Tensor:
+        """Generates max_new_tokens tokens behind prompt_ids ([P] or [bsz, P]) from an empty cache, with the decode attention on.  The loop body (decode_step_auto +
+        sampler + token feed) is captured ONCE as a graph and replayed P - 1 + max_new_tokens times without a synchronisation or a host read in between (the
+        prompt goes through the same step token by token as forced tokens; feeding it through prefill_chunk is a follow-up); one read at the end.  One
+        uncaptured step runs first (decode_step_persistent checks a new plan's first run for time-outs only outside capture); the state is reset after it.
+        settings: sampling.SamplerSettings (None = greedy).  Returns int64 [n] / [bsz, n]: the new tokens, for one sequence trimmed behind the first
+        eos_token_id (kept), for a batch filled with eos_token_id behind it.  Raises if a row went invalid (NaN logits: a timed-out persistent step)."""
+        from . import sampling
+        if self.tp > 1:
+            raise NotImplementedError("generate: tensor-parallel sampling (the vocabulary gather) is not built")
+        if self.shape.head_dim not in (64, 128):
+            raise NotImplementedError("generate: the decode attention takes head_dim 64 or 128")
+        prompt = torch.as_tensor(prompt_ids, dtype=torch.long)
+        one = prompt.dim() == 1
+        if one:
+            prompt = prompt.unsqueeze(0)
+        bsz, P = prompt.shape
+        ka = (settings or sampling.SamplerSettings(temperature=0.0)).kernel_args()
+        att_before = self.with_attention
+        self.with_attention = True
+        try:
+            gs = self.alloc_gen_state(bsz, max_new_tokens, prompt)
+            self.gen_stats = {"graph_captures": 0, "graph_replays": 0, "host_reads": 0}
+            if gs.total > 0:
+                self.gen_step(ka)                              # uncaptured: plan creation, the persistent step's first-run check (may fall back, loudly)
+                self._gen_prime()
+                st = torch.cuda.Stream(device=self.device)
+                st.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(st):
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, stream=st):
+                        self.gen_step(ka)
+                torch.cuda.current_stream(self.device).wait_stream(st)
+                self.gen_stats["graph_captures"] = 1
+                for _ in range(gs.total):
+                    graph.replay()
+                    self.gen_stats["graph_replays"] += 1
+            host = torch.cat([gs.tokens_out, gs.invalid.view(bsz, 1)], dim=1).cpu()           # the one read (synchronises)
+            self.gen_stats["host_reads"] = 1
+        finally:
+            self.with_attention = att_before
+        toks, invalid = host[:, :gs.total].long(), host[:, -1]
+        if bool(invalid.any()):
+            ps = getattr(self, "_pstep", None)
+            if ps is not None and ps.tp is None and ps.error():
+                import warnings
+                warnings.warn("exllamav3_amd: the persistent decode step timed out (its logits were NaN-poisoned); using the launch-per-op pipeline from here on", RuntimeWarning)
+                type(self).persistent = False
+                self.persistent = False
+                self._pstep = None
+            raise RuntimeError(f"generate: rows {[int(i) for i in invalid.nonzero().flatten()]} produced an invalid token (NaN / Inf logits)")
+        new = toks[:, P - 1:]
+        if eos_token_id is not None:
+            for r in range(bsz):
+                hit = (new[r] == eos_token_id).nonzero().flatten()
+                if hit.numel():
+                    if one:
+                        new = new[:, :int(hit[0]) + 1]
+                    else:
+                        new[r, int(hit[0]) + 1:] = eos_token_id
+        return new[0] if one else new
 
     #: tensor-parallel ranks take the fx pipeline too (round 4): 7 launches per layer instead of the glue pipeline's 8-10
     fx_under_tp = os.environ.get("EXL3_HIP_FX_UNDER_TP", "1") != "0"

@@ -709,6 +709,32 @@ int exl3_pstep_describe(void* handle, char* buf, int buf_bytes);
 int64_t exl3_pstep_stamps(void* handle, uint64_t* host_out, int64_t max_words, void* stream);
 int exl3_pstep_destroy(void* handle);
 
+/* ---- device-side token generation (exl3_sampler.hip)    generator/sampling_fused.cu:11-30,156-173, sampling_basic.cu, gumbel.cu ----------------------
+ * exl3_sample: one token per row of fp16 logits [m][ld] (m = 1..16, ld a multiple of 8, 16-byte aligned); columns >= size (the head's padding) never win and never count.
+ *   mode 0  greedy: the largest logit, lowest index among equals.
+ *   mode 1  argmax_i (l_i * inv_temp + g_i), g_i Gumbel(0, 1): a sample of softmax(l * inv_temp); ties to the lowest index.
+ *   mode 2  mode 1 over { i : l_i >= fp32(M + minp_log) }, M the row maximum.
+ *   mode 3  mode 1 over { i : l_i >= cutoff }: filters bit 0 top-k (cutoff = the k-th largest logit with multiplicity, exact, ties kept), bit 2 min-p (as mode 2),
+ *           bit 1 top-p over what those two left (sampling_fused.cuh:12-15), weights w_i = exp((l_i - M) * inv_temp_filter) summed as 2^40 fixed point in u64: a
+ *           value class stays while the mass down to and including it is <= top_p * Z; the top class always stays.
+ *   A row holding NaN or +Inf below `size`, or nothing above -Inf, yields token -1; -Inf entries are never chosen.
+ *   Noise: Philox4x32-10, key (seed_lo, seed_hi), counter (column, row0 + row, step low word, step high word), output word 0, u = ((w >> 9) + 0.5) * 2^-23,
+ *   g = -log(-log(u)).  `step` is a DEVICE word (NULL = 0) read by the kernel, so a replayed graph draws fresh noise; the noise depends neither on m nor on the grid.
+ *   This is the library's own stream, not curand's.
+ *   workspace: device memory of exl3_sample_workspace(m) bytes, ZERO-FILLED before its first use (the calls leave it so); calls sharing it must be stream-ordered.
+ *   cutoff_out (the smallest kept logit) / kept_out (size of the kept set): optional, per row.  Graph-capturable, allocates nothing.
+ *   Launches: modes 0 / 1 one, modes 2 / 3 two.  No workgroup waits for another (the last of a row's workgroups to arrive combines their partial results).
+ * exl3_gen_feed: one launch behind the sampler.  Per row: token = forced[row][step + 1] while step + 1 < forced_len (prompt / teacher forcing), else sampled[row];
+ *   tokens_out[row][step] = token (0 <= step < out_len); x0[row] = embed[token] (fp16 [vocab][hidden]); positions / cache_seqlens / attn_lens [row] += 1 (each optional);
+ *   finally *step += 1.  A token outside [0, vocab) never indexes the table: the row keeps its input, invalid[row] is set (sticky) and -1 is recorded from then on. */
+int exl3_sample_workspace(int m, int64_t* bytes);
+int exl3_sample(const void* logits, int m, int ld, int size, int mode, int filters, int top_k, float top_p, float inv_temp, float inv_temp_filter,
+                float minp_log, uint32_t seed_lo, uint32_t seed_hi, const int64_t* step, int row0, void* workspace, int64_t workspace_bytes,
+                int32_t* tokens, float* cutoff_out, int32_t* kept_out, void* stream);
+int exl3_gen_feed(const int32_t* sampled, const int32_t* forced, int forced_len, int m, const void* embed, int vocab, int hidden, void* x0,
+                  int32_t* tokens_out, int out_len, int32_t* positions, int32_t* cache_seqlens, int32_t* attn_lens, int32_t* invalid, int64_t* step,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,204 @@
+#!/usr/bin/env python3
+"""Measures the device-side generation path on the GPU and writes profiles/generate_bench.json:
+
+  sampler   exl3_sample per mode at m = 1 and 16 rows of 128 256 fp16 logits against torch doing the same job on the same logits in the same process
+            (argmax; softmax + multinomial; top-k / sort + cumsum for top-p).  exl3_sample as a graph of 50 calls (device time), torch as eager launches in a tight loop.
+  generate  tokens/s of the replayed generation loop (decode step + sampler + token feed in one graph, no host read) against the host-stepped loop (graph of the
+            decode step, logits copied to the host, numpy argmax, counters advanced from the host), bench.py's --attention configuration (4 bpw mul1, 4-bit cache)
+            at the 8B and 1B shapes, 8-token prompt + 256 new tokens from an empty cache.
+
+Method: device events around whole windows that end in a synchronise, every shape warmed up, windows of at least --window seconds, the two sides of a comparison
+alternating in one process, min / median / max of the repeated windows reported.  A run without a GPU fails."""
+import argparse
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+V = 128256
+CALLS = 50
+
+
+def spread(xs):
+    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4), "windows": len(xs)}
+
+
+def timed_window(fn, reps):
+    """ms of `reps` calls of fn between two device events; ends in a synchronise."""
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1)
+
+
+def graph_of(fn, calls):
+    import torch
+    fn(); torch.cuda.synchronize()
+    st = torch.cuda.Stream(); st.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(st):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=st):
+            for _ in range(calls):
+                fn()
+    torch.cuda.current_stream().wait_stream(st)
+    torch.cuda.synchronize()
+    return g
+
+
+def alternate(sides, window_s, repeats):
+    """sides: {name: (callable, units per call)} -> {name: spread of us per unit}; windows of >= window_s each, the sides alternating."""
+    reps = {}
+    for name, (fn, units) in sides.items():
+        fn(); fn()
+        t = timed_window(fn, 3) / 3
+        reps[name] = max(1, math.ceil(window_s * 1e3 / max(t, 1e-3)))
+    out = {name: [] for name in sides}
+    for _ in range(repeats):
+        for name, (fn, units) in sides.items():
+            out[name].append(timed_window(fn, reps[name]) * 1e3 / (reps[name] * units))
+    return {name: dict(spread(v), unit="us", calls_per_window=reps[name] * sides[name][1]) for name, v in out.items()}
+
+
+def bench_sampler(dev, args):
+    import torch
+    from exllamav3_amd import sampling
+    res = {}
+    gen = torch.Generator(device=dev); gen.manual_seed(1)
+    for m in (1, 16):
+        logits = (torch.randn((m, V), device=dev, generator=gen) * 3.0).half()
+        stepw = torch.zeros((1,), dtype=torch.int64, device=dev)
+        out = torch.empty((m,), dtype=torch.int32, device=dev)
+        ws = sampling.workspace(m, dev)
+        S = sampling.SamplerSettings
+
+        def t_greedy(): return torch.argmax(logits, dim=-1)
+        def t_sample(): return torch.multinomial(torch.softmax(logits.float() * 1.25, dim=-1), 1)
+
+        def t_minp():
+            p = torch.softmax(logits.float(), dim=-1)
+            p = torch.where(p >= 0.05 * p.amax(dim=-1, keepdim=True), p, torch.zeros_like(p))
+            return torch.multinomial(torch.softmax(torch.log(p) * 1.25, dim=-1), 1)
+
+        def t_topk_topp():
+            v, i = torch.topk(logits.float(), 50, dim=-1)
+            p = torch.softmax(v * 1.25, dim=-1)
+            c = torch.cumsum(p, dim=-1)
+            keep = c <= 0.9
+            keep[:, 0] = True
+            return torch.gather(i, 1, torch.multinomial(torch.where(keep, p, torch.zeros_like(p)), 1))
+
+        def t_topp():
+            v, i = torch.sort(logits.float(), dim=-1, descending=True)
+            p = torch.softmax(v * 1.25, dim=-1)
+            c = torch.cumsum(p, dim=-1)
+            keep = c <= 0.9
+            keep[:, 0] = True
+            return torch.gather(i, 1, torch.multinomial(torch.where(keep, p, torch.zeros_like(p)), 1))
+
+        cases = [("mode0_greedy", S(temperature=0.0), t_greedy), ("mode1_sample", S(temperature=0.8), t_sample), ("mode2_minp", S(temperature=0.8, min_p=0.05), t_minp),
+                 ("mode3_topk50_topp0.9", S(temperature=0.8, top_k=50, top_p=0.9), t_topk_topp), ("mode3_topp0.9", S(temperature=0.8, top_p=0.9), t_topp)]
+        for name, st, tfn in cases:
+            ka = st.kernel_args()
+            ours = graph_of(lambda: sampling.sample(logits, ka, stepw, out=out, ws=ws), CALLS)
+            # torch's side as eager launches in a tight loop (its ops allocate their results; what a caller of torch gets without writing a capture of his own)
+            r = alternate({"exl3_sample": (ours.replay, CALLS), "torch_eager": (tfn, 1)}, args.window, args.repeats)
+            r["mode"], r["launches"] = ka.mode, (1 if ka.mode < 2 else 2)
+            res[f"m{m}_{name}"] = r
+            print(f"m{m}_{name}", json.dumps(r), flush=True)
+    return res
+
+
+def bench_generate(dev, args, shape_name):
+    import numpy as np
+    import torch
+    from exllamav3_amd import sampling
+    from exllamav3_amd.llama_path import SHAPES, SyntheticEXL3Llama
+    m = SyntheticEXL3Llama(SHAPES[shape_name], K=4, cb=2, device=dev, kv_bits=4, layers=args.layers or None)
+    m.with_attention = True
+    prompt = torch.tensor([[128000, 9906, 11, 856, 836, 374, 1234, 77]])
+    P, new = prompt.shape[1], args.new_tokens
+    total = P - 1 + new
+    ka = sampling.SamplerSettings(temperature=0.0).kernel_args()
+    ka_s = sampling.SamplerSettings(temperature=0.8, top_k=50, top_p=0.9, seed=1).kernel_args()
+    gs = m.alloc_gen_state(1, new, prompt)
+    table = m.embed_table()
+    m.gen_step(ka); torch.cuda.synchronize()
+    persistent = m._pstep is not None and not m._pstep.error()
+    graphs = {}
+    for nm, k in (("greedy", ka), ("sampled", ka_s)):
+        m._gen_prime()
+        graphs[nm] = graph_of(lambda: m.gen_step(k), 1)
+    m._gen_prime()
+    g_step = graph_of(m.decode_step_auto, 1)
+
+    def device_loop(nm):
+        m._gen_prime()
+        for _ in range(total):
+            graphs[nm].replay()
+
+    def host_loop():
+        toks = prompt[0].tolist()
+        tok = toks[0]
+        for s in range(total):
+            m.positions.fill_(s); m.cache_seqlens.fill_(s); m.attn_lens.fill_(s + 1)
+            m.x0.copy_(table[tok].view(1, -1))
+            g_step.replay()
+            l = m.logits[0].cpu().numpy()
+            tok = toks[s + 1] if s + 1 < P else int(np.argmax(l[:V]))
+
+    device_loop("greedy"); torch.cuda.synchronize()
+    dev_tokens = gs.tokens_out[0].cpu().tolist()
+    r = alternate({"device_loop_greedy": (lambda: device_loop("greedy"), total), "host_stepped_loop_greedy": (host_loop, total),
+                   "device_loop_topk50_topp0.9": (lambda: device_loop("sampled"), total)}, args.window, args.repeats)
+    out = {"shape": shape_name, "layers": m.n_layers, "prompt_tokens": P, "new_tokens": new, "steps_per_generation": total, "persistent_step": bool(persistent),
+           "invalid_rows": int(gs.invalid.sum()), "first_tokens": dev_tokens[P - 1:P + 7]}
+    for k, v in r.items():
+        out[k] = dict(v, unit="us per step", tokens_per_s=round(1e6 / v["median"], 1))
+    print(shape_name, json.dumps(out), flush=True)
+    del m, graphs, g_step
+    torch.cuda.empty_cache()
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window (at least)")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--new-tokens", type=int, default=256)
+    ap.add_argument("--layers", type=int, default=0, help="debug: fewer layers (invalidates the number)")
+    ap.add_argument("--skip", default="", help="comma list of: sampler, 8b, 1b")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generate_bench.json"))
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_generate.py: needs a GPU")
+    from exllamav3_amd import ext
+    dev = torch.device("cuda:0")
+    ext.init(0)
+    ext.set_gemv_variant(1)
+    skip = set(args.skip.split(","))
+    res = {"device": torch.cuda.get_device_name(0), "method": "device events around windows ending in a synchronise; >= %.1f s per window; sides alternating; %d windows per side"
+           % (args.window, args.repeats), "when": time.strftime("%Y-%m-%d")}
+    if "sampler" not in skip:
+        res["sampler_us_per_call"] = bench_sampler(dev, args)
+    res["generate"] = {}
+    for nm, shape in (("8b", "llama-3.1-8b"), ("1b", "llama-3.2-1b")):
+        if nm not in skip:
+            res["generate"][shape] = bench_generate(dev, args, shape)
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
