@@ -230,6 +230,9 @@ def _declare(l):
     sig("exl3_sample_workspace", i32, ctypes.POINTER(i64))
     sig("exl3_sample", vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, u32, u32, vp, i32, vp, i64, vp, vp, vp, vp)
     sig("exl3_gen_feed", vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp)
+    sig("exl3_gen_feed_stop", vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp)
+    # logit processors (exl3_logit_process.hip)
+    sig("exl3_logit_process", vp, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, i32, f32, i32, i32, f32, f32, i32, i32, vp, vp, i32, i32, vp)
     sig("exl3_set_gemv_variant", i32)
     sig("exl3_set_gemv_max_waves", i32)
     sig("exl3_set_gemv_gen4", i32)

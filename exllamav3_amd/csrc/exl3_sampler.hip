@@ -392,6 +392,62 @@ void gen_feed_kernel(const int32_t* __restrict__ sampled, const int32_t* __restr
     if (tid == 0) *step_ptr = step + 1;
 }
 
+// exl3_gen_feed with stop tokens: a row whose SAMPLED token is one of stop_ids becomes done (sticky).  The stop token is recorded but not fed: from that step on
+// the row's input, positions and lengths stay as they are (the step keeps rewriting one cache slot) and tokens_out receives pad_token.  live = rows neither done
+// nor invalid behind this step.
+#define GEN_MAX_STOP 64
+__global__ __launch_bounds__(1024)
+void gen_feed_stop_kernel(const int32_t* __restrict__ sampled, const int32_t* __restrict__ forced, int forced_len, int m, const half_t* __restrict__ embed, int vocab,
+                          int hidden, half_t* __restrict__ x0, int32_t* __restrict__ tokens_out, int out_len, int32_t* __restrict__ positions,
+                          int32_t* __restrict__ cache_seqlens, int32_t* __restrict__ attn_lens, int32_t* __restrict__ invalid, long long* __restrict__ step_ptr,
+                          const int32_t* __restrict__ stop_ids, int n_stop, int32_t* __restrict__ done, int pad_token, int32_t* __restrict__ live)
+{
+    __shared__ int tok_s[SMP_MAX_ROWS];
+    __shared__ int live_s[SMP_MAX_ROWS];
+    const int tid = threadIdx.x;
+    const long long step = *step_ptr;
+    if (tid < m)
+    {
+        int tok = -1, feed = -1;
+        if (done[tid]) tok = pad_token;
+        else
+        {
+            bool is_sampled = false;
+            if (forced && step + 1 >= 0 && step + 1 < forced_len) tok = forced[(size_t) tid * forced_len + (step + 1)];
+            else if (sampled) { tok = sampled[tid]; is_sampled = true; }
+            if (tok < 0 || tok >= vocab || invalid[tid]) { tok = -1; invalid[tid] = 1; }        // sticky: never indexes the table
+            bool stop = false;
+            if (is_sampled && tok >= 0)
+                for (int k = 0; k < n_stop; ++k) stop = stop || stop_ids[k] == tok;
+            if (stop) done[tid] = 1;
+            else
+            {
+                feed = tok;
+                if (positions) positions[tid] += 1;
+                if (cache_seqlens) cache_seqlens[tid] += 1;
+                if (attn_lens) attn_lens[tid] += 1;
+            }
+        }
+        tok_s[tid] = feed;
+        live_s[tid] = !done[tid] && !invalid[tid];
+        if (tokens_out && step >= 0 && step < out_len) tokens_out[(size_t) tid * out_len + step] = tok;
+    }
+    __syncthreads();
+    const int per_row = hidden / 8;
+    for (int i = tid; i < m * per_row; i += 1024)
+    {
+        const int r = i / per_row, c = i - r * per_row, tok = tok_s[r];
+        if (tok >= 0) ((uint4_t*) (x0 + (size_t) r * hidden))[c] = ((const uint4_t*) (embed + (size_t) tok * hidden))[c];
+    }
+    if (tid == 0)
+    {
+        int n = 0;
+        for (int r = 0; r < m; ++r) n += live_s[r];
+        *live = n;
+        *step_ptr = step + 1;
+    }
+}
+
 extern "C" int exl3_sample_workspace(int m, int64_t* bytes)
 {
     EXL3_CHECK_ARG(m >= 1 && m <= SMP_MAX_ROWS && bytes, "exl3_sample_workspace: m must be in [1, 16]");
@@ -447,4 +503,22 @@ extern "C" int exl3_gen_feed(const int32_t* sampled, const int32_t* forced, int 
     gen_feed_kernel<<<1, 1024, 0, (hipStream_t) stream>>>(sampled, forced, forced ? forced_len : 0, m, (const half_t*) embed, vocab, hidden, (half_t*) x0, tokens_out,
                                                           tokens_out ? out_len : 0, positions, cache_seqlens, attn_lens, invalid, (long long*) step);
     return exl3_check_launch("gen_feed");
+}
+
+extern "C" int exl3_gen_feed_stop(const int32_t* sampled, const int32_t* forced, int forced_len, int m, const void* embed, int vocab, int hidden, void* x0,
+                                  int32_t* tokens_out, int out_len, int32_t* positions, int32_t* cache_seqlens, int32_t* attn_lens, int32_t* invalid, int64_t* step,
+                                  const int32_t* stop_ids, int n_stop, int32_t* done, int pad_token, int32_t* live, void* stream)
+{
+    EXL3_CHECK_ARG(m >= 1 && m <= SMP_MAX_ROWS, "exl3_gen_feed_stop: m must be in [1, 16]");
+    EXL3_CHECK_ARG(embed && x0 && invalid && step && done && live, "exl3_gen_feed_stop: null pointer");
+    EXL3_CHECK_ARG(sampled || forced, "exl3_gen_feed_stop: needs sampled or forced tokens");
+    EXL3_CHECK_ARG(vocab >= 1 && hidden >= 8 && hidden % 8 == 0, "exl3_gen_feed_stop: hidden must be a multiple of 8");
+    EXL3_CHECK_ARG((((uintptr_t) embed | (uintptr_t) x0) & 15) == 0, "exl3_gen_feed_stop: embed / x0 must be 16-byte aligned");
+    EXL3_CHECK_ARG(!forced || forced_len >= 1, "exl3_gen_feed_stop: forced_len must be at least 1");
+    EXL3_CHECK_ARG(!tokens_out || out_len >= 1, "exl3_gen_feed_stop: out_len must be at least 1");
+    EXL3_CHECK_ARG(n_stop >= 0 && n_stop <= GEN_MAX_STOP && (n_stop == 0 || stop_ids), "exl3_gen_feed_stop: at most 64 stop ids");
+    gen_feed_stop_kernel<<<1, 1024, 0, (hipStream_t) stream>>>(sampled, forced, forced ? forced_len : 0, m, (const half_t*) embed, vocab, hidden, (half_t*) x0, tokens_out,
+                                                               tokens_out ? out_len : 0, positions, cache_seqlens, attn_lens, invalid, (long long*) step, stop_ids, n_stop,
+                                                               done, pad_token, live);
+    return exl3_check_launch("gen_feed_stop");
 }

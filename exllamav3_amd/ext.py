@@ -1232,6 +1232,68 @@ def softcap(x, y, scale: float):
 
 
 # --------------------------------------------------------------------------------------------------
+# logit processors (exl3_logit_process.hip): the reference's deterministic sampler ops under their own names
+# --------------------------------------------------------------------------------------------------
+
+def _past_ids_i32(past_ids: torch.Tensor, in_logits: torch.Tensor, name: str) -> torch.Tensor:
+    _req(past_ids.dtype == torch.long, f"{name}: past_ids has incorrect data type")
+    _req(in_logits.dim() == 2 and in_logits.size(0) == 1, "rep. penalties only implemented for bsz 1")
+    _req(past_ids.dim() == 2 and past_ids.size(0) == 1, f"{name}: past_ids and in_logits have incompatible shapes")
+    # the kernel reads int32 ids; whatever does not fit is outside every vocabulary and ignored like any other out-of-range id
+    return past_ids.to(in_logits.device).clamp(-1, 2 ** 31 - 1).to(torch.int32).contiguous()
+
+
+def _pen_checks(in_logits, out_logits, name: str):
+    _dev(in_logits)
+    _req(out_logits.dtype == torch.float, f"{name}: out_logits has incorrect data type")
+    _req(in_logits.dtype in (torch.half, torch.float), f"{name}: in_logits must be float16 or float32")
+    _req(in_logits.shape == out_logits.shape and in_logits.is_contiguous() and out_logits.is_contiguous(), f"{name}: in_logits and out_logits have incompatible shapes")
+
+
+def apply_rep_pens(in_logits, out_logits, past_ids, rep_p: float, sustain_range: int, decay_range: int):
+    """rep_pen.cu:93-134 (same argument order): repetition penalty over past_ids [1, n] (int64), fp16 / fp32 in, fp32 out, batch 1; in place when out is in.  The
+    window weights are integers here (include/exl3_hip.h: exl3_logit_process): equal to the reference up to fp32 rounding."""
+    _pen_checks(in_logits, out_logits, "apply_rep_pens")
+    ids = _past_ids_i32(past_ids, in_logits, "apply_rep_pens")
+    n, v = ids.shape[1], in_logits.shape[1]
+    _check(_lib.lib().exl3_logit_process(_p(in_logits), int(in_logits.dtype == torch.float), _p(out_logits), 1, 1, v, v, None, 0, 0, _p(ids) if n else None, n, n, None, 0,
+                                         float(rep_p), int(sustain_range), int(decay_range), 0.0, 0.0, 0, 0, None, None, 0, 0, _stream(in_logits)))
+
+
+def apply_pres_freq_pens(in_logits, out_logits, past_ids, pres_p: float, freq_p: float, sustain_range: int, decay_range: int):
+    """rep_pen.cu:203-246 (same argument order): presence / frequency penalties over past_ids [1, n] (int64), fp16 / fp32 in, fp32 out, batch 1.  The frequency
+    sum is an integer sum here (order-independent): equal to the reference up to the fp32 rounding of its order-dependent running sum."""
+    _pen_checks(in_logits, out_logits, "apply_pres_freq_pens")
+    ids = _past_ids_i32(past_ids, in_logits, "apply_pres_freq_pens")
+    n, v = ids.shape[1], in_logits.shape[1]
+    _check(_lib.lib().exl3_logit_process(_p(in_logits), int(in_logits.dtype == torch.float), _p(out_logits), 1, 1, v, v, None, 0, 0, _p(ids) if n else None, n, n, None, 0,
+                                         1.0, 0, 0, float(pres_p), float(freq_p), int(sustain_range), int(decay_range), None, None, 0, 0, _stream(in_logits)))
+
+
+def apply_logit_bitmask(logits_in, logits_out, bitmask):
+    """sampling_fused.cu:976-1020 (same argument order): logits_out = logits_in where the token's bit is set, -inf elsewhere; fp16 or fp32 (one type on both
+    sides), bitmask int32 [1 or bsz][words]."""
+    _dev(logits_in)
+    _req(logits_in.dim() == 2, "apply_logit_bitmask: logits must have 2 dimensions")
+    _req(logits_in.is_contiguous(), "apply_logit_bitmask: logits must be contiguous")
+    _req(logits_out.is_contiguous(), "apply_logit_bitmask: output must be contiguous")
+    _req(logits_out.shape == logits_in.shape, "apply_logit_bitmask: shape mismatch")
+    _req(logits_out.dtype == logits_in.dtype, "apply_logit_bitmask: dtype mismatch")
+    _req(bitmask.dtype == torch.int32, "apply_logit_bitmask: bitmask has incorrect data type")
+    _req(bitmask.dim() == 2 and bitmask.is_contiguous(), "apply_logit_bitmask: bitmask must be contiguous and have 2 dimensions")
+    bsz, dim = logits_in.shape
+    _req(bitmask.size(0) in (1, bsz), "apply_logit_bitmask: bad bitmask batch dim")
+    _req(logits_in.dtype in (torch.half, torch.float), "apply_logit_bitmask: logits must be half or float")
+    fp32 = int(logits_in.dtype == torch.float)
+    words = bitmask.size(1)
+    for r0 in range(0, bsz, 16):                                         # the kernel takes 16 rows per launch
+        rows = min(16, bsz - r0)
+        bm = bitmask if bitmask.size(0) == 1 else bitmask[r0:r0 + rows]
+        _check(_lib.lib().exl3_logit_process(_p(logits_in[r0:]), fp32, _p(logits_out[r0:]), fp32, rows, dim, dim, None, 0, 0, None, 0, 0, None, 0,
+                                             1.0, 0, 0, 0.0, 0.0, 0, 0, None, _p(bm), 1 if bitmask.size(0) == 1 else rows, words, _stream(logits_in)))
+
+
+# --------------------------------------------------------------------------------------------------
 # fused decode pipeline (deferred-epilogue GEMVs + glue kernels); see include/exl3_hip.h
 # --------------------------------------------------------------------------------------------------
 

@@ -1010,7 +1010,9 @@ class SyntheticEXL3Llama:
             P=P, total=P - 1 + max_new, embed=embed, forced=prompt.to(torch.int32).to(dev).contiguous(),
             tokens_out=torch.empty((bsz, total), dtype=torch.int32, device=dev), sampled=torch.empty((bsz,), dtype=torch.int32, device=dev),
             invalid=torch.empty((bsz,), dtype=torch.int32, device=dev), step=torch.empty((1,), dtype=torch.int64, device=dev),
-            ws=sampling.workspace(bsz, dev))
+            ws=sampling.workspace(bsz, dev),
+            # stop tokens (exl3_gen_feed_stop) and logit processors (exl3_logit_process): used only when generate() is given them
+            done=torch.zeros((bsz,), dtype=torch.int32, device=dev), live=torch.full((1,), bsz, dtype=torch.int32, device=dev), stop_ids=None, proc_logits=None)
         self._gen_prime()
         return self.gen
 
@@ -1020,24 +1022,39 @@ class SyntheticEXL3Llama:
         gs = self.gen
         self.positions.fill_(-1); self.cache_seqlens.fill_(-1); self.attn_lens.fill_(0)
         gs.step.fill_(-1); gs.invalid.zero_(); gs.tokens_out.fill_(-1); gs.sampled.fill_(-1)
+        gs.done.zero_(); gs.live.fill_(self.x0.shape[0])
         sampling.gen_feed(None, gs.forced, gs.embed, self.x0, None, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step, vocab=self.shape.vocab)
 
-    def gen_step(self, ka):
-        """The loop body of generate(): decode step, sampler, token feed -- kernel launches only (graph-capturable)."""
+    def gen_step(self, ka, processors=None, stop: bool = False):
+        """The loop body of generate(): decode step, (logit processors,) sampler, token feed -- kernel launches only (graph-capturable).  processors: the sampler
+        reads a second buffer that exl3_logit_process fills from the step's logits and the tokens fed so far (forced[:, 0], then tokens_out[:, :step word]).
+        stop: the feed is exl3_gen_feed_stop over gs.stop_ids / gs.done / gs.live."""
         from . import sampling
         gs = self.gen
         logits = self.decode_step_auto()
+        if processors is not None:
+            logits = sampling.process_logits(logits, processors, gs.forced[:, 0:1], gs.tokens_out, step=gs.step, size=self.shape.vocab, out=gs.proc_logits)
         sampling.sample(logits, ka, gs.step, size=self.shape.vocab, out=gs.sampled, ws=gs.ws)
-        sampling.gen_feed(gs.sampled, gs.forced, gs.embed, self.x0, gs.tokens_out, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step,
-                          vocab=self.shape.vocab)
+        if stop:
+            sampling.gen_feed(gs.sampled, gs.forced, gs.embed, self.x0, gs.tokens_out, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step,
+                              vocab=self.shape.vocab, stop_ids=gs.stop_ids, done=gs.done, pad_token=gs.pad_token, live=gs.live)
+        else:
+            sampling.gen_feed(gs.sampled, gs.forced, gs.embed, self.x0, gs.tokens_out, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step,
+                              vocab=self.shape.vocab)
 
-    def generate(self, prompt_ids, max_new_tokens: int, settings=None, eos_token_id: int | None = None) -> torch.Tensor:
+    def generate(self, prompt_ids, max_new_tokens: int, settings=None, eos_token_id: int | None = None, processors=None, stop_token_ids=None,
+                 stop_check_every: int | None = None) -> torch.Tensor:
         """Generates max_new_tokens tokens behind prompt_ids ([P] or [bsz, P]) from an empty cache, with the decode attention on.  The loop body (decode_step_auto +
         sampler + token feed) is captured ONCE as a graph and replayed P - 1 + max_new_tokens times without a synchronisation or a host read in between (the
         prompt goes through the same step token by token as forced tokens; feeding it through prefill_chunk is a follow-up); one read at the end.  One
         uncaptured step runs first (decode_step_persistent checks a new plan's first run for time-outs only outside capture); the state is reset after it.
         settings: sampling.SamplerSettings (None = greedy).  Returns int64 [n] / [bsz, n]: the new tokens, for one sequence trimmed behind the first
-        eos_token_id (kept), for a batch filled with eos_token_id behind it.  Raises if a row went invalid (NaN logits: a timed-out persistent step)."""
+        eos_token_id (kept), for a batch filled with eos_token_id behind it.  Raises if a row went invalid (NaN logits: a timed-out persistent step).
+        processors: sampling.LogitProcessors -- one more launch per token (exl3_logit_process) between the step and the sampler, still no host read.
+        stop_token_ids (<= 64 ids): the feed marks a row done at its first SAMPLED stop token (a stop id inside the prompt does not count); after every
+        stop_check_every replays (default 16) the host reads the 4-byte live word and leaves the loop when no row is live.  The result follows the EOS rules: one
+        sequence is cut behind its first stop token (kept), a batch is filled with the first stop id behind it.  gen_stats counts the reads of the live word in
+        host_reads and gains stopped_after (the replay count at which the loop was left early, else None) on this path only."""
         from . import sampling
         if self.tp > 1:
             raise NotImplementedError("generate: tensor-parallel sampling (the vocabulary gather) is not built")
@@ -1049,27 +1066,50 @@ class SyntheticEXL3Llama:
             prompt = prompt.unsqueeze(0)
         bsz, P = prompt.shape
         ka = (settings or sampling.SamplerSettings(temperature=0.0)).kernel_args()
+        if processors is not None and processors.is_noop:
+            processors = None
+        stop = None
+        if stop_token_ids is not None:
+            stop = [int(t) for t in stop_token_ids]
+            if not (1 <= len(stop) <= sampling.MAX_STOP_IDS):
+                raise ValueError("generate: 1 to 64 stop token ids")
+            every = 16 if stop_check_every is None else int(stop_check_every)
+            if every < 1:
+                raise ValueError("generate: stop_check_every must be at least 1")
+        elif stop_check_every is not None:
+            raise ValueError("generate: stop_check_every needs stop_token_ids")
         att_before = self.with_attention
         self.with_attention = True
         try:
             gs = self.alloc_gen_state(bsz, max_new_tokens, prompt)
             self.gen_stats = {"graph_captures": 0, "graph_replays": 0, "host_reads": 0}
+            if stop is not None:
+                self.gen_stats["stopped_after"] = None
+                gs.stop_ids = torch.tensor(stop, dtype=torch.int32, device=self.device)
+                gs.pad_token = stop[0]
+            if processors is not None:
+                gs.proc_logits = torch.empty_like(self.logits)
             if gs.total > 0:
-                self.gen_step(ka)                              # uncaptured: plan creation, the persistent step's first-run check (may fall back, loudly)
+                self.gen_step(ka, processors, stop is not None)    # uncaptured: plan creation, the persistent step's first-run check (may fall back, loudly)
                 self._gen_prime()
                 st = torch.cuda.Stream(device=self.device)
                 st.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(st):
                     graph = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(graph, stream=st):
-                        self.gen_step(ka)
+                        self.gen_step(ka, processors, stop is not None)
                 torch.cuda.current_stream(self.device).wait_stream(st)
                 self.gen_stats["graph_captures"] = 1
-                for _ in range(gs.total):
+                for i in range(gs.total):
                     graph.replay()
                     self.gen_stats["graph_replays"] += 1
+                    if stop is not None and (i + 1) % every == 0 and i + 1 < gs.total:
+                        self.gen_stats["host_reads"] += 1
+                        if int(gs.live.cpu()) == 0:                # the 4-byte live word (synchronises)
+                            self.gen_stats["stopped_after"] = i + 1
+                            break
             host = torch.cat([gs.tokens_out, gs.invalid.view(bsz, 1)], dim=1).cpu()           # the one read (synchronises)
-            self.gen_stats["host_reads"] = 1
+            self.gen_stats["host_reads"] += 1
         finally:
             self.with_attention = att_before
         toks, invalid = host[:, :gs.total].long(), host[:, -1]
@@ -1083,6 +1123,15 @@ class SyntheticEXL3Llama:
                 self._pstep = None
             raise RuntimeError(f"generate: rows {[int(i) for i in invalid.nonzero().flatten()]} produced an invalid token (NaN / Inf logits)")
         new = toks[:, P - 1:]
+        if stop is not None:
+            cut = new.shape[1]
+            for r in range(bsz):
+                hit = torch.isin(new[r], torch.tensor(stop)).nonzero().flatten()
+                if hit.numel():
+                    new[r, int(hit[0]) + 1:] = stop[0]
+                    cut = int(hit[0]) + 1
+            if one:
+                new = new[:, :cut]
         if eos_token_id is not None:
             for r in range(bsz):
                 hit = (new[r] == eos_token_id).nonzero().flatten()

@@ -1,5 +1,6 @@
 """
-Device-side sampling (csrc/exl3_sampler.hip; include/exl3_hip.h: exl3_sample / exl3_gen_feed).
+Device-side sampling (csrc/exl3_sampler.hip, csrc/exl3_logit_process.hip; include/exl3_hip.h: exl3_sample / exl3_gen_feed / exl3_gen_feed_stop /
+exl3_logit_process).
 
 SamplerSettings collapses a (temperature, top-k, top-p, min-p) stack into the kernel's (mode, filters, ...) the way the reference collapses a sampler
 stack into its fused sampler (generator/sampler/custom.py:267-343): greedy when nothing can change the top token, a Gumbel sample of softmax(l / T)
@@ -7,6 +8,10 @@ otherwise, restricted to one cutoff for min-p alone (mode 2) or for any combinat
 
 The noise is this library's own Philox4x32-10 stream keyed by (seed; column, row, step) -- NOT curand's sequence, so the reference's op names
 (argmax_sample, gumbel_sample, fused_sampler, gumbel_noise_*) are deliberately absent from exllamav3_amd.ext.
+
+LogitProcessors is what runs in front of the sampler: repetition and presence / frequency penalties over the tokens generated so far, a logit bias with banned
+tokens, a packed token bitmask -- the deterministic steps of the reference's sampler stack (custom.py: SS_RepP, SS_PresFreqP, SS_LogitBias, SS_BanTokens and the
+grammar filters' bitmask), collapsed the way the reference collapses them and applied by ONE launch (process_logits -> exl3_logit_process).
 """
 from __future__ import annotations
 import ctypes
@@ -108,9 +113,13 @@ def sample(logits: torch.Tensor, settings: SamplerSettings | KernelArgs | None =
 
 
 def gen_feed(sampled, forced, embed: torch.Tensor, x0: torch.Tensor, tokens_out, positions, cache_seqlens, attn_lens, invalid: torch.Tensor, step: torch.Tensor,
-             vocab: int | None = None):
+             vocab: int | None = None, *, stop_ids: torch.Tensor | None = None, done: torch.Tensor | None = None, pad_token: int | None = None,
+             live: torch.Tensor | None = None):
     """The launch behind the sampler: per row the next token (forced[row, step + 1] while the forced list lasts, else sampled[row]) -> tokens_out[row, step],
-    x0[row] = embed[token], the three counters and the step word + 1.  A token outside [0, vocab) leaves x0 alone and sets the sticky invalid[row]."""
+    x0[row] = embed[token], the three counters and the step word + 1.  A token outside [0, vocab) leaves x0 alone and sets the sticky invalid[row].
+    With stop_ids (int32, <= 64), done (int32 [m], sticky), pad_token and live (one int32 word) the launch is exl3_gen_feed_stop: a row whose SAMPLED token is a
+    stop id becomes done -- the token is recorded, not fed; from then on the row's input and counters freeze and tokens_out receives pad_token; live = rows neither
+    done nor invalid.  Without them the launch is exl3_gen_feed, unchanged."""
     m, hidden = x0.shape
     ok = embed.dtype == torch.half and x0.dtype == torch.half and embed.is_contiguous() and x0.is_contiguous() and embed.dim() == 2 and embed.shape[1] == hidden
     for t in (sampled, forced, tokens_out, positions, cache_seqlens, attn_lens, invalid):
@@ -122,6 +131,134 @@ def gen_feed(sampled, forced, embed: torch.Tensor, x0: torch.Tensor, tokens_out,
         raise RuntimeError("gen_feed: fp16 embed [vocab, hidden] / x0 [m, hidden], int32 token / counter tensors with m rows, an int64 step word")
     if x0.device.index != torch.cuda.current_device():
         torch.cuda.set_device(x0.device)
-    _check(_lib.lib().exl3_gen_feed(_p(sampled), _p(forced), forced.shape[1] if forced is not None else 0, m, _p(embed), int(embed.shape[0] if vocab is None else vocab),
-                                    hidden, _p(x0), _p(tokens_out), tokens_out.shape[1] if tokens_out is not None else 0, _p(positions), _p(cache_seqlens),
-                                    _p(attn_lens), _p(invalid), _p(step), torch.cuda.current_stream(x0.device).cuda_stream))
+    args = (_p(sampled), _p(forced), forced.shape[1] if forced is not None else 0, m, _p(embed), int(embed.shape[0] if vocab is None else vocab),
+            hidden, _p(x0), _p(tokens_out), tokens_out.shape[1] if tokens_out is not None else 0, _p(positions), _p(cache_seqlens),
+            _p(attn_lens), _p(invalid), _p(step))
+    if stop_ids is None and done is None and live is None and pad_token is None:
+        _check(_lib.lib().exl3_gen_feed(*args, torch.cuda.current_stream(x0.device).cuda_stream))
+        return
+    if stop_ids is None or done is None or live is None or pad_token is None:
+        raise RuntimeError("gen_feed: stop_ids, done, pad_token and live go together")
+    for t, n in ((stop_ids, 0), (done, m), (live, 1)):
+        if not (t.dtype == torch.int32 and t.is_contiguous() and t.device == x0.device and t.numel() >= n):
+            raise RuntimeError("gen_feed: stop_ids / done [m] / live [1] must be contiguous int32 tensors on the device of x0")
+    _check(_lib.lib().exl3_gen_feed_stop(*args, _p(stop_ids), stop_ids.numel(), _p(done), int(pad_token), _p(live), torch.cuda.current_stream(x0.device).cuda_stream))
+
+
+MAX_STOP_IDS = 64
+_F32_MAX = float(torch.finfo(torch.float32).max)
+
+
+class LogitProcessors:
+    """What exl3_logit_process applies to a row of logits, in this order: repetition penalty (rep_p; 1 = off) and presence / frequency penalties (pres_p, freq_p;
+    0 = off) over the past tokens, each with its own (sustain, decay) window as in the reference (custom.py: SS_RepP, SS_PresFreqP); logit_bias {id: value}
+    (-inf bans) with ban_token_ids folded in as -inf; bitmask: an int32 / uint32 tensor [1 or m][words], bit set = keep (apply_logit_bitmask's layout) -- a tensor
+    already on the device is used where it lies, so a grammar filter may rewrite it between replays.
+    No-ops collapse by the reference's rules: rep_p == 1 or sustain + decay <= 0 switches the repetition penalty off (custom.py:790-793), pres_p == freq_p == 0
+    or sustain + decay <= 0 the other (:855-858); bias entries that are 0, NaN or overflow fp32 to +inf are dropped (:586-595); ids outside the vocabulary are
+    ignored.  The device tensors are built once per (vocabulary, device)."""
+
+    def __init__(self, rep_p: float = 1.0, rep_sustain: int = 10 ** 8, rep_decay: int = 0, pres_p: float = 0.0, freq_p: float = 0.0, pf_sustain: int = 10 ** 8,
+                 pf_decay: int = 0, logit_bias: dict | None = None, ban_token_ids=None, bitmask: torch.Tensor | None = None):
+        rep_p, pres_p, freq_p = float(rep_p), float(pres_p), float(freq_p)
+        if not (math.isfinite(rep_p) and rep_p > 0.0 and math.isfinite(pres_p) and math.isfinite(freq_p)):
+            raise ValueError("LogitProcessors: rep_p must be positive and finite, pres_p and freq_p finite")
+        for nm, v in (("rep_sustain", rep_sustain), ("rep_decay", rep_decay), ("pf_sustain", pf_sustain), ("pf_decay", pf_decay)):
+            if int(v) != v or not (0 <= int(v) < 2 ** 31):
+                raise ValueError(f"LogitProcessors: {nm} must be an integer in [0, 2^31)")
+        if int(rep_sustain) + int(rep_decay) >= 2 ** 31 or int(pf_sustain) + int(pf_decay) >= 2 ** 31:
+            raise ValueError("LogitProcessors: sustain + decay must fit an int32")
+        self.rep_on = rep_p != 1.0 and int(rep_sustain) + int(rep_decay) > 0
+        self.pf_on = (pres_p != 0.0 or freq_p != 0.0) and int(pf_sustain) + int(pf_decay) > 0
+        # a penalty that is off reaches the kernel as its neutral element
+        self.rep_p, self.rep_sustain, self.rep_decay = (rep_p, int(rep_sustain), int(rep_decay)) if self.rep_on else (1.0, 0, 0)
+        self.pres_p, self.freq_p, self.pf_sustain, self.pf_decay = (pres_p, freq_p, int(pf_sustain), int(pf_decay)) if self.pf_on else (0.0, 0.0, 0, 0)
+        bias = {}
+        for t, v in (logit_bias or {}).items():
+            v = float(v)
+            if v != 0.0 and v == v and v <= _F32_MAX:
+                bias[int(t)] = v
+        for t in (ban_token_ids if ban_token_ids is not None else ()):
+            bias[int(t)] = float("-inf")
+        self.bias = bias
+        if bitmask is not None:
+            if not (isinstance(bitmask, torch.Tensor) and bitmask.dtype in (torch.int32, torch.uint32) and bitmask.dim() == 2 and bitmask.shape[1] >= 1
+                    and bitmask.is_contiguous()):
+                raise ValueError("LogitProcessors: bitmask must be a contiguous int32 / uint32 tensor [1 or m][words]")
+        self.bitmask = bitmask
+        self._vectors = {}
+
+    @property
+    def needs_history(self) -> bool:
+        return self.rep_on or self.pf_on
+
+    @property
+    def is_noop(self) -> bool:
+        return not (self.rep_on or self.pf_on or self.bias or self.bitmask is not None)
+
+    def tensors(self, vocab: int, device):
+        """(bias fp32 [vocab] or None, bitmask on `device` or None), cached per (vocab, device)."""
+        device = torch.device(device)
+        key = (int(vocab), device)
+        got = self._vectors.get(key)
+        if got is None:
+            items = [(t, v) for t, v in self.bias.items() if 0 <= t < vocab]
+            vec = None
+            if items:
+                vec = torch.zeros((vocab,), dtype=torch.float)
+                vec[torch.tensor([t for t, _ in items], dtype=torch.long)] = torch.tensor([v for _, v in items], dtype=torch.float)
+                vec = vec.to(device)
+            bm = self.bitmask
+            if bm is not None and bm.device != device:
+                bm = bm.to(device)
+            got = self._vectors[key] = (vec, bm)
+        return got
+
+
+def process_logits(logits: torch.Tensor, procs: LogitProcessors, past_a: torch.Tensor | None = None, past_b: torch.Tensor | None = None, len_b: int | None = None,
+                   step: torch.Tensor | None = None, *, size: int | None = None, len_b_bias: int = 0, out: torch.Tensor | None = None) -> torch.Tensor:
+    """procs applied to fp16 / fp32 `logits` [m, ld] (m <= 16) -> `out` (fp16 / fp32, default: a new tensor of the input's type; may be `logits` itself).  The past
+    ids of row r are past_a[r, :] followed by past_b[r, :len_b], int32 (past_a may be a column view such as forced[:, 0:1]); the length of the second segment is
+    the host integer len_b (default: all of past_b) or, with `step` (a DEVICE int64 word), clamp(step + len_b_bias, 0, past_b.shape[1]) read by the kernel.  One
+    launch, graph-capturable when `out` is given (the bias vector is built at the first call for a vocabulary: call once outside the capture)."""
+    if not (logits.is_cuda and logits.dtype in (torch.half, torch.float) and logits.dim() == 2 and logits.is_contiguous()):
+        raise RuntimeError("process_logits: logits must be a contiguous (m, ld) float16 / float32 tensor on the GPU")
+    m, ld = logits.shape
+    size = int(ld if size is None else size)
+    if out is None:
+        out = torch.empty_like(logits)
+    if not (out.is_cuda and out.device == logits.device and out.dtype in (torch.half, torch.float) and out.shape == logits.shape and out.is_contiguous()):
+        raise RuntimeError("process_logits: out must be a contiguous float16 / float32 tensor of the logits' shape on their device")
+    seg = []
+    for t, nm in ((past_a, "past_a"), (past_b, "past_b")):
+        if t is None:
+            seg.append((None, 0, 0))
+            continue
+        if not (t.dtype == torch.int32 and t.dim() == 2 and t.shape[0] == m and t.device == logits.device and (t.shape[1] == 0 or t.stride(1) == 1)):
+            raise RuntimeError(f"process_logits: {nm} must be an int32 [m, n] tensor on the logits' device with unit column stride")
+        ldt = t.stride(0) if (m > 1 and t.shape[1] > 0) else t.shape[1]
+        if ldt < t.shape[1]:
+            raise RuntimeError(f"process_logits: rows of {nm} overlap")
+        seg.append((t.data_ptr() if t.shape[1] > 0 else None, int(ldt), int(t.shape[1])))
+    (pa, lda, len_a), (pb, ldb, cap_b) = seg
+    if step is not None:
+        if not (step.dtype == torch.int64 and step.numel() == 1 and step.device == logits.device):
+            raise RuntimeError("process_logits: step must be one int64 word on the logits' device")
+        if past_b is None or len_b is not None or ldb != cap_b:
+            raise RuntimeError("process_logits: the device length needs a contiguous past_b and no host len_b")
+        lb = 0
+    else:
+        lb = cap_b if len_b is None else int(len_b)
+        if not (0 <= lb <= cap_b):
+            raise RuntimeError("process_logits: len_b outside past_b")
+    bias, bm = procs.tensors(size, logits.device)
+    if bm is not None and bm.shape[0] not in (1, m):
+        raise RuntimeError("process_logits: the bitmask has 1 or m rows")
+    if logits.device.index != torch.cuda.current_device():
+        torch.cuda.set_device(logits.device)
+    _check(_lib.lib().exl3_logit_process(_p(logits), int(logits.dtype == torch.float), _p(out), int(out.dtype == torch.float), m, ld, size,
+                                         pa, lda, len_a, pb, ldb, lb, _p(step), int(len_b_bias),
+                                         procs.rep_p, procs.rep_sustain, procs.rep_decay, procs.pres_p, procs.freq_p, procs.pf_sustain, procs.pf_decay,
+                                         _p(bias), _p(bm), 0 if bm is None else bm.shape[0], 0 if bm is None else bm.shape[1],
+                                         torch.cuda.current_stream(logits.device).cuda_stream))
+    return out

@@ -735,6 +735,38 @@ int exl3_gen_feed(const int32_t* sampled, const int32_t* forced, int forced_len,
                   int32_t* tokens_out, int out_len, int32_t* positions, int32_t* cache_seqlens, int32_t* attn_lens, int32_t* invalid, int64_t* step,
                   void* stream);
 
+/* exl3_gen_feed_stop: exl3_gen_feed with stop tokens (the reference stops on the host, generator/job.py; here the loop has no host in it).  A row becomes done
+ *   (done[row], sticky) when the token it takes at this step is a SAMPLED one (the forced list is used up: a stop id inside the prompt never stops a row) and is one
+ *   of stop_ids (int32, n_stop <= 64).  The stop token is written to tokens_out and is not fed: from that step on x0[row] and the row's positions / cache_seqlens /
+ *   attn_lens stay as they are, and tokens_out[row][step] = pad_token at every later step.  *step advances as always.  *live = rows neither done nor invalid
+ *   behind this step, written at every step. */
+int exl3_gen_feed_stop(const int32_t* sampled, const int32_t* forced, int forced_len, int m, const void* embed, int vocab, int hidden, void* x0,
+                       int32_t* tokens_out, int out_len, int32_t* positions, int32_t* cache_seqlens, int32_t* attn_lens, int32_t* invalid, int64_t* step,
+                       const int32_t* stop_ids, int n_stop, int32_t* done, int pad_token, int32_t* live, void* stream);
+
+/* ---- logit processors (exl3_logit_process.hip)    generator/rep_pen.cu (apply_rep_pens, apply_pres_freq_pens), generator/sampling_fused.cu:951-1020
+ *      (apply_logit_bitmask), generator/sampler/custom.py:581-609 (LogitBias) -----------------------------------------------------------------------------
+ * exl3_logit_process: one launch, rows r = 0 .. m - 1 (m = 1..16): logits_in [m][ld] (fp16, or fp32 when in_fp32) -> logits_out [m][ld] (fp16 / fp32 by out_fp32;
+ *   may be logits_in when the types match).  ld a multiple of 8, both 16-byte aligned; columns [size, ld) of the output are written -Inf.
+ *   History of row r: past_a[r * lda + 0 .. len_a) followed by past_b[r * ldb + 0 .. len_b), int32.  With len_b_dev (a DEVICE int64 word, e.g. the generation loop's
+ *   step word) len_b = clamp(*len_b_dev + len_b_bias, 0, ldb) is read by the kernel, so a replayed graph sees the history grow; else the host len_b holds.
+ *   n = len_a + len_b (0 is legal); ids outside [0, size) are ignored.
+ *   Window (S = sustain, D = decay, both >= 0, S + D an int32): the past token at index i has dist = n - i (1 = newest); it counts iff dist < S + D (rep_pen.cu:51,
+ *   :168; with D = 0 that is dist <= S - 1) with the integer weight num = Dn if dist <= S else D - (dist - S), over Dn = max(D, 1).  pmax[t] = max num, fsum[t] =
+ *   sum of num over the counting occurrences of id t: integers, so the result depends neither on arrival order nor on grid or batch.  Refused when fsum could
+ *   pass 2^32: min(S + D, len_a + ldb) * Dn >= 2^32.
+ *   Arithmetic in fp32, every operation rounded on its own, v = float(logit):
+ *     1. repetition (rep_p != 1, rep S + D > 0; pmax_rep[t] > 0, v finite): w = v > 0 ? v / rep_p : v * rep_p; f = float(pmax) / float(Dn); v = v * (1 - f) + w * f
+ *     2. presence / frequency (pres_p or freq_p != 0, pf S + D > 0; pmax_pf[t] > 0, v finite): v = (v - freq_p * (float(fsum) / float(Dn))) - pres_p * (float(pmax) / float(Dn))
+ *     3. bias (fp32 [size], optional): v = v + bias[t] (-Inf bans)
+ *     4. bitmask (uint32 [bitmask_rows = 1 or m][bitmask_words], bit set = keep, optional): v = -Inf where the bit is clear or t >= 32 * bitmask_words
+ *     5. one round-to-nearest-even conversion to the output type.
+ *   A non-finite v passes 1 - 2 unchanged.  Graph-capturable, allocates nothing, no workspace; no workgroup waits for another. */
+int exl3_logit_process(const void* logits_in, int in_fp32, void* logits_out, int out_fp32, int m, int ld, int size,
+                       const int32_t* past_a, int lda, int len_a, const int32_t* past_b, int ldb, int len_b, const int64_t* len_b_dev, int len_b_bias,
+                       float rep_p, int rep_sustain, int rep_decay, float pres_p, float freq_p, int pf_sustain, int pf_decay,
+                       const float* bias, const uint32_t* bitmask, int bitmask_rows, int bitmask_words, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

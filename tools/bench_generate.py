@@ -7,6 +7,10 @@
             decode step, logits copied to the host, numpy argmax, counters advanced from the host), bench.py's --attention configuration (4 bpw mul1, 4-bit cache)
             at the 8B and 1B shapes, 8-token prompt + 256 new tokens from an empty cache.
 
+  processors  exl3_logit_process alone at m = 1 and 16 rows of 128 256 fp16 logits (penalties over a 1024-token window; bias + bitmask only), as a graph of 50
+            calls; the replayed generation loop with processors on against the same loop without them (the two alternating), and generate() under a 256-token
+            budget that stops at token ~20 (stop_token_ids) against the same call without stop ids (replays and wall time, capture included).
+
 Method: device events around whole windows that end in a synchronise, every shape warmed up, windows of at least --window seconds, the two sides of a comparison
 alternating in one process, min / median / max of the repeated windows reported.  A run without a GPU fails."""
 import argparse
@@ -169,13 +173,94 @@ def bench_generate(dev, args, shape_name):
     return out
 
 
+def bench_logit_process(dev, args):
+    import numpy as np
+    import torch
+    from exllamav3_amd import sampling
+    res = {}
+    gen = torch.Generator(device=dev); gen.manual_seed(2)
+    rng = np.random.default_rng(2)
+    bias = {int(t): float(v) for t, v in zip(rng.integers(0, V, 300), rng.standard_normal(300))}
+    for m in (1, 16):
+        logits = (torch.randn((m, V), device=dev, generator=gen) * 3.0).half()
+        out = torch.empty_like(logits)
+        past = torch.randint(0, V, (m, 2048), device=dev, generator=gen).to(torch.int32)
+        stepw = torch.full((1,), 2048, dtype=torch.int64, device=dev)
+        bm = torch.randint(-2 ** 31, 2 ** 31 - 1, (m, (V + 31) // 32), device=dev, generator=gen).to(torch.int32)
+        pen = sampling.LogitProcessors(rep_p=1.3, rep_sustain=512, rep_decay=512, pres_p=0.2, freq_p=0.3, pf_sustain=1024, pf_decay=0)
+        bb = sampling.LogitProcessors(logit_bias=bias, ban_token_ids=[1, 2, 3], bitmask=bm)
+        allp = sampling.LogitProcessors(rep_p=1.3, rep_sustain=512, rep_decay=512, pres_p=0.2, freq_p=0.3, pf_sustain=1024, pf_decay=0, logit_bias=bias, bitmask=bm)
+        sides = {}
+        for nm, pr in (("penalties_window1024", pen), ("bias_bitmask", bb), ("all", allp)):
+            g = graph_of(lambda pr=pr: sampling.process_logits(logits, pr, None, past, step=stepw, out=out), CALLS)
+            sides[nm] = (g.replay, CALLS)
+        r = alternate(sides, args.window, args.repeats)
+        for nm, v in r.items():
+            res[f"m{m}_{nm}"] = v
+            print(f"logit_process m{m}_{nm}", json.dumps(v), flush=True)
+    return res
+
+
+def bench_generate_processors(dev, args, shape_name):
+    import torch
+    from exllamav3_amd import sampling
+    from exllamav3_amd.llama_path import SHAPES, SyntheticEXL3Llama
+    m = SyntheticEXL3Llama(SHAPES[shape_name], K=4, cb=2, device=dev, kv_bits=4, layers=args.layers or None)
+    m.with_attention = True
+    prompt = torch.tensor([[128000, 9906, 11, 856, 836, 374, 1234, 77]])
+    P, new = prompt.shape[1], args.new_tokens
+    total = P - 1 + new
+    ka = sampling.SamplerSettings(temperature=0.0).kernel_args()
+    procs = sampling.LogitProcessors(rep_p=1.3, rep_sustain=512, rep_decay=512, pres_p=0.2, freq_p=0.3, pf_sustain=1024, pf_decay=0, logit_bias={12345: 2.0},
+                                     ban_token_ids=[128001, 128009])
+    gs = m.alloc_gen_state(1, new, prompt)
+    gs.proc_logits = torch.empty_like(m.logits)
+    m.gen_step(ka, procs); torch.cuda.synchronize()
+    graphs = {}
+    for nm, pr in (("off", None), ("on", procs)):
+        m._gen_prime()
+        graphs[nm] = graph_of(lambda pr=pr: m.gen_step(ka, pr), 1)
+
+    def device_loop(nm):
+        m._gen_prime()
+        for _ in range(total):
+            graphs[nm].replay()
+
+    r = alternate({"device_loop_greedy": (lambda: device_loop("off"), total), "device_loop_greedy_processors": (lambda: device_loop("on"), total)},
+                  args.window, args.repeats)
+    out = {"shape": shape_name, "layers": m.n_layers, "steps_per_generation": total, "invalid_rows": int(gs.invalid.sum())}
+    for k, v in r.items():
+        out[k] = dict(v, unit="us per step", tokens_per_s=round(1e6 / v["median"], 1))
+    out["processors_cost_us_per_step"] = round(out["device_loop_greedy_processors"]["median"] - out["device_loop_greedy"]["median"], 3)
+    del graphs
+    # the stop path: generate() under a 256-token budget, stopped at token ~20 (wall time of the whole call: allocation, the uncaptured step, the capture, the replays)
+    m.with_attention = False
+    plain = m.generate(prompt[0], new)
+    stop = int(plain[20])
+    first = plain.tolist().index(stop)
+    stop_res = {"stop_token_index": first}
+    for nm, kw in (("without_stop_ids", {}), ("with_stop_ids", {"stop_token_ids": [stop]})):
+        walls = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = m.generate(prompt[0], new, **kw)
+            walls.append((time.perf_counter() - t0) * 1e3)
+        stop_res[nm] = {"wall_ms": spread(walls), "graph_replays": m.gen_stats["graph_replays"], "host_reads": m.gen_stats["host_reads"], "tokens_returned": int(got.numel())}
+    out["stop_path"] = stop_res
+    print("processors", shape_name, json.dumps(out), flush=True)
+    del m
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window (at least)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--new-tokens", type=int, default=256)
     ap.add_argument("--layers", type=int, default=0, help="debug: fewer layers (invalidates the number)")
-    ap.add_argument("--skip", default="", help="comma list of: sampler, 8b, 1b")
+    ap.add_argument("--skip", default="", help="comma list of: sampler, 8b, 1b, processors (a skipped section keeps what --out already holds)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generate_bench.json"))
     args = ap.parse_args()
     import torch
@@ -186,14 +271,21 @@ def main():
     ext.init(0)
     ext.set_gemv_variant(1)
     skip = set(args.skip.split(","))
-    res = {"device": torch.cuda.get_device_name(0), "method": "device events around windows ending in a synchronise; >= %.1f s per window; sides alternating; %d windows per side"
-           % (args.window, args.repeats), "when": time.strftime("%Y-%m-%d")}
+    res = {}
+    if os.path.exists(args.out):
+        with open(args.out) as f:
+            res = json.load(f)
+    res.update({"device": torch.cuda.get_device_name(0), "method": "device events around windows ending in a synchronise; >= %.1f s per window; sides alternating; %d windows per side"
+           % (args.window, args.repeats), "when": time.strftime("%Y-%m-%d")})
     if "sampler" not in skip:
         res["sampler_us_per_call"] = bench_sampler(dev, args)
-    res["generate"] = {}
+    res.setdefault("generate", {})
     for nm, shape in (("8b", "llama-3.1-8b"), ("1b", "llama-3.2-1b")):
         if nm not in skip:
             res["generate"][shape] = bench_generate(dev, args, shape)
+    if "processors" not in skip:
+        res["logit_process_us_per_call"] = bench_logit_process(dev, args)
+        res["generate_processors"] = {shape: bench_generate_processors(dev, args, shape) for shape in ("llama-3.1-8b", "llama-3.2-1b")}
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
