@@ -231,6 +231,7 @@ def _declare(l):
     sig("exl3_sample", vp, i32, i32, i32, i32, i32, i32, f32, f32, f32, f32, u32, u32, vp, i32, vp, i64, vp, vp, vp, vp)
     sig("exl3_gen_feed", vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp)
     sig("exl3_gen_feed_stop", vp, vp, i32, i32, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, vp)
+    sig("exl3_embed_rows", vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp)
     # logit processors (exl3_logit_process.hip)
     sig("exl3_logit_process", vp, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, i32, f32, i32, i32, f32, f32, i32, i32, vp, vp, i32, i32, vp)
     sig("exl3_set_gemv_variant", i32)

@@ -448,6 +448,23 @@ void gen_feed_stop_kernel(const int32_t* __restrict__ sampled, const int32_t* __
     }
 }
 
+// ---- prompt ids -> input rows of a prefill chunk --------------------------------------------------------------------------------------------------------------
+// out[b * T + t] = embed[ids[b][col0 + t]]: one workgroup per output row, 16-byte copies.  The feed's rules for a bad id: it never indexes the table, the row is
+// written as zeros and invalid[b] is set (only ever set here, so rows of one sequence may race on it).
+__global__ __launch_bounds__(256)
+void embed_rows_kernel(const int32_t* __restrict__ ids, int ld_ids, int col0, int T, const half_t* __restrict__ embed, int vocab, int hidden,
+                       half_t* __restrict__ out, int32_t* __restrict__ invalid)
+{
+    const int row = blockIdx.x, b = row / T, t = row - b * T;
+    const int tok = ids[(size_t) b * ld_ids + col0 + t];
+    const bool ok = tok >= 0 && tok < vocab;
+    if (!ok && threadIdx.x == 0) invalid[b] = 1;
+    const uint4_t* src = (const uint4_t*) (embed + (size_t) (ok ? tok : 0) * hidden);
+    uint4_t* dst = (uint4_t*) (out + (size_t) row * hidden);
+    const uint4_t zero = {0u, 0u, 0u, 0u};
+    for (int c = threadIdx.x; c < hidden / 8; c += 256) dst[c] = ok ? src[c] : zero;
+}
+
 extern "C" int exl3_sample_workspace(int m, int64_t* bytes)
 {
     EXL3_CHECK_ARG(m >= 1 && m <= SMP_MAX_ROWS && bytes, "exl3_sample_workspace: m must be in [1, 16]");
@@ -521,4 +538,18 @@ extern "C" int exl3_gen_feed_stop(const int32_t* sampled, const int32_t* forced,
                                                                tokens_out ? out_len : 0, positions, cache_seqlens, attn_lens, invalid, (long long*) step, stop_ids, n_stop,
                                                                done, pad_token, live);
     return exl3_check_launch("gen_feed_stop");
+}
+
+extern "C" int exl3_embed_rows(const int32_t* ids, int ld_ids, int col0, int T, int m, const void* embed, int vocab, int hidden, void* out, int32_t* invalid,
+                               void* stream)
+{
+    EXL3_CHECK_ARG(m >= 1 && m <= SMP_MAX_ROWS, "exl3_embed_rows: m must be in [1, 16]");
+    EXL3_CHECK_ARG(ids && embed && out && invalid, "exl3_embed_rows: null pointer");
+    EXL3_CHECK_ARG(T >= 1, "exl3_embed_rows: T must be at least 1");
+    EXL3_CHECK_ARG(col0 >= 0 && (int64_t) col0 + T <= ld_ids, "exl3_embed_rows: columns [col0, col0 + T) must lie inside the id matrix");
+    EXL3_CHECK_ARG(vocab >= 1 && hidden >= 8 && hidden % 8 == 0, "exl3_embed_rows: hidden must be a multiple of 8");
+    EXL3_CHECK_ARG((((uintptr_t) embed | (uintptr_t) out) & 15) == 0, "exl3_embed_rows: embed / out must be 16-byte aligned");
+    EXL3_CHECK_ARG((int64_t) m * T <= 0x7fffffff, "exl3_embed_rows: too many rows");
+    embed_rows_kernel<<<m * T, 256, 0, (hipStream_t) stream>>>(ids, ld_ids, col0, T, (const half_t*) embed, vocab, hidden, (half_t*) out, invalid);
+    return exl3_check_launch("embed_rows");
 }

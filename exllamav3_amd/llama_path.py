@@ -1042,11 +1042,87 @@ class SyntheticEXL3Llama:
             sampling.gen_feed(gs.sampled, gs.forced, gs.embed, self.x0, gs.tokens_out, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step,
                               vocab=self.shape.vocab)
 
+    #: tokens per row of one ingestion chunk of generate(prompt_mode="prefill").  Measured (tools/bench_generate.py, section prompt; 8191 prompt tokens, ingest_prompt
+    #: alone): 512 / 1024 / 2048 / 4096 -> 29.5k / 42.8k / 59.5k / 72.1k tok/s on Llama-3.1-8B, 104k / 185k / 271k / 353k on Llama-3.2-1B: the largest wins (the
+    #: weights are reconstructed once per chunk).  EXL3_HIP_GEN_PREFILL_CHUNK overrides it for A/B runs.
+    gen_prefill_chunk = int(os.environ.get("EXL3_HIP_GEN_PREFILL_CHUNK", "4096"))
+
+    def ingest_prompt(self, n_tokens: int, chunk: int | None = None, return_rows: bool = False):
+        """Prompt tokens 0 .. n_tokens - 1 of every row of the generation state (alloc_gen_state: gs.forced) through the PREFILL route into the generation's own
+        cache (self.kcache / self.vcache per layer, through the state's block_table), at most `chunk` tokens per row at a time (default gen_prefill_chunk).  A chunk
+        at offset p0 with T tokens: rows from exl3_embed_rows, then per layer RMSNorm -> q|k|v -> RoPE at p0 .. p0 + T - 1 -> quantised append behind
+        cache_seqlens = p0 -> dequant_cache_paged into ONE fp16 expansion buffer shared by all layers (bsz * max_ctx rows) -> causal attention with lengths
+        p0 + T -> o_proj (+ residual) -> norm -> gate|up -> down (+ residual).  Any T >= 1 works (LinearEXL3 routes by row count).  In the last chunk the last layer
+        stops behind its cache append: nothing downstream of it is consumed (no final norm, no lm_head).  return_rows (tests): every layer runs to its end and the
+        residual stream behind the last layer comes back as fp16 [bsz, n_tokens, hidden].
+        Leaves positions = cache_seqlens = n_tokens and attn_lens = n_tokens + 1 (what a decode step of token n_tokens expects).  Returns the chunk count (or the rows)."""
+        from . import sampling
+        if self.tp > 1:
+            raise NotImplementedError("ingest_prompt: tensor-parallel generation is not built")
+        s, hd, dev = self.shape, self.shape.head_dim, self.device
+        if hd not in (64, 128):
+            raise NotImplementedError("ingest_prompt: the prefill attention takes head_dim 64 or 128")
+        gs, bsz = self.gen, self._state_bsz
+        n = int(n_tokens)
+        chunk = int(self.gen_prefill_chunk if chunk is None else chunk)
+        if chunk < 1:
+            raise ValueError("ingest_prompt: chunk must be at least 1")
+        if not (0 <= n <= gs.forced.shape[1] and n <= self.max_ctx):
+            raise ValueError("ingest_prompt: n_tokens outside the prompt")
+        kv_dim = self.hkv * hd
+        n_pages = self.block_table.numel()
+        if getattr(self, "_ing_pages", None) is None or self._ing_pages[0].shape != (n_pages, self.page, kv_dim):
+            self._ing_pages = [torch.zeros((n_pages, self.page, kv_dim), dtype=torch.half, device=dev) for _ in range(2)]
+        kd, vd = self._ing_pages
+        out, chunks = [], 0
+        for p0 in range(0, n, chunk):
+            T = min(chunk, n - p0)
+            self.cache_seqlens.fill_(p0)
+            self.attn_lens.fill_(p0 + T)
+            x = sampling.embed_rows(gs.forced, p0, T, gs.embed, gs.invalid, vocab=s.vocab)
+            xn = torch.empty_like(x)
+            ao = torch.empty((bsz * T, self.hq * hd), dtype=torch.half, device=dev)
+            for li, L in enumerate(self.layers):
+                ext.rms_norm(x, L["norm1"], xn, self.eps)
+                last = p0 + T == n and li == self.n_layers - 1 and not return_rows
+                q = self._prefill_qkv_attend(L, xn, bsz, T, p0, self.kcache[li], self.vcache[li], self.cache_seqlens, self.block_table,
+                                             None if last else (kd, vd, self.attn_lens, ao))
+                if last:
+                    break
+                L["o"].forward_add_residual(q, x)
+                ext.rms_norm(x, L["norm2"], xn, self.eps)
+                a = type(L["gate"]).forward_gate_up_silu(L["gate"], L["up"], xn)
+                L["down"].forward_add_residual(a, x)
+            chunks += 1
+            if return_rows:
+                out.append(x.view(bsz, T, s.hidden))
+        self.positions.fill_(n); self.cache_seqlens.fill_(n); self.attn_lens.fill_(n + 1)
+        return torch.cat(out, dim=1) if return_rows else chunks
+
+    def _gen_prime_prefilled(self, chunk: int | None = None) -> int:
+        """_gen_prime for generate(prompt_mode="prefill"): prompt tokens 0 .. P - 2 go through ingest_prompt, then the state is set to what P - 2 replays of the
+        loop leave (step word = positions = cache_seqlens = P - 2, attn_lens = P - 1, tokens_out[:, :P - 2] = prompt[:, 1:P - 1]) and ONE feed without sampled
+        tokens does the rest as it does in the loop: forced[:, P - 1] -> x0 and tokens_out[:, P - 2], every counter + 1.  Integer for integer the state behind
+        P - 1 replays, so the logit processors see the same history and the sampler the same step words.  Returns the chunk count."""
+        from . import sampling
+        gs, P = self.gen, self.gen.P
+        assert P >= 2, "nothing to ingest"
+        self._gen_prime()
+        chunks = self.ingest_prompt(P - 1, chunk)
+        self.positions.fill_(P - 2); self.cache_seqlens.fill_(P - 2); self.attn_lens.fill_(P - 1)
+        gs.step.fill_(P - 2)
+        gs.tokens_out[:, :P - 2] = gs.forced[:, 1:P - 1]
+        sampling.gen_feed(None, gs.forced, gs.embed, self.x0, gs.tokens_out, self.positions, self.cache_seqlens, self.attn_lens, gs.invalid, gs.step, vocab=self.shape.vocab)
+        return chunks
+
     def generate(self, prompt_ids, max_new_tokens: int, settings=None, eos_token_id: int | None = None, processors=None, stop_token_ids=None,
-                 stop_check_every: int | None = None) -> torch.Tensor:
+                 stop_check_every: int | None = None, prompt_mode: str = "decode", prefill_chunk: int | None = None) -> torch.Tensor:
         """Generates max_new_tokens tokens behind prompt_ids ([P] or [bsz, P]) from an empty cache, with the decode attention on.  The loop body (decode_step_auto +
         sampler + token feed) is captured ONCE as a graph and replayed P - 1 + max_new_tokens times without a synchronisation or a host read in between (the
-        prompt goes through the same step token by token as forced tokens; feeding it through prefill_chunk is a follow-up); one read at the end.  One
+        prompt goes through the same step token by token as forced tokens: prompt_mode "decode", the default); one read at the end.
+        prompt_mode "prefill": prompt tokens 0 .. P - 2 go through the prefill route instead (ingest_prompt, chunks of prefill_chunk tokens per row, default
+        gen_prefill_chunk), one feed hands the state over (_gen_prime_prefilled) and the captured body is replayed max_new_tokens times; gen_stats gains
+        prefill_tokens (bsz * (P - 1)) and prefill_chunks on this path only.  With P == 1 there is nothing to ingest: decode mode.  One
         uncaptured step runs first (decode_step_persistent checks a new plan's first run for time-outs only outside capture); the state is reset after it.
         settings: sampling.SamplerSettings (None = greedy).  Returns int64 [n] / [bsz, n]: the new tokens, for one sequence trimmed behind the first
         eos_token_id (kept), for a batch filled with eos_token_id behind it.  Raises if a row went invalid (NaN logits: a timed-out persistent step).
@@ -1056,6 +1132,8 @@ class SyntheticEXL3Llama:
         sequence is cut behind its first stop token (kept), a batch is filled with the first stop id behind it.  gen_stats counts the reads of the live word in
         host_reads and gains stopped_after (the replay count at which the loop was left early, else None) on this path only."""
         from . import sampling
+        if prompt_mode not in ("decode", "prefill"):
+            raise ValueError('generate: prompt_mode is "decode" or "prefill"')
         if self.tp > 1:
             raise NotImplementedError("generate: tensor-parallel sampling (the vocabulary gather) is not built")
         if self.shape.head_dim not in (64, 128):
@@ -1089,9 +1167,15 @@ class SyntheticEXL3Llama:
                 gs.pad_token = stop[0]
             if processors is not None:
                 gs.proc_logits = torch.empty_like(self.logits)
-            if gs.total > 0:
+            prefill = prompt_mode == "prefill" and P > 1
+            replays = max_new_tokens if prefill else gs.total
+            if replays > 0:
                 self.gen_step(ka, processors, stop is not None)    # uncaptured: plan creation, the persistent step's first-run check (may fall back, loudly)
-                self._gen_prime()
+                if prefill:
+                    self.gen_stats["prefill_chunks"] = self._gen_prime_prefilled(prefill_chunk)
+                    self.gen_stats["prefill_tokens"] = bsz * (P - 1)
+                else:
+                    self._gen_prime()
                 st = torch.cuda.Stream(device=self.device)
                 st.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(st):
@@ -1100,10 +1184,10 @@ class SyntheticEXL3Llama:
                         self.gen_step(ka, processors, stop is not None)
                 torch.cuda.current_stream(self.device).wait_stream(st)
                 self.gen_stats["graph_captures"] = 1
-                for i in range(gs.total):
+                for i in range(replays):
                     graph.replay()
                     self.gen_stats["graph_replays"] += 1
-                    if stop is not None and (i + 1) % every == 0 and i + 1 < gs.total:
+                    if stop is not None and (i + 1) % every == 0 and i + 1 < replays:
                         self.gen_stats["host_reads"] += 1
                         if int(gs.live.cpu()) == 0:                # the 4-byte live word (synchronises)
                             self.gen_stats["stopped_after"] = i + 1
@@ -1411,6 +1495,38 @@ class SyntheticEXL3Llama:
         return self.layers[0]["o"].default_out_dtype
 
     # ---- one prefill chunk -----------------------------------------------------------------------------
+    def _prefill_qkv_attend(self, L, xn, bsz: int, T: int, p0: int, kcache, vcache, seqlens, block_table, attend):
+        """The attention half of a prefill layer over rows xn [bsz * T, hidden] (row b * T + t = token p0 + t of sequence b), shared by prefill_chunk and
+        ingest_prompt: q|k|v (one GEMM where forward_multi applies, else three linears), RoPE at positions p0 .. p0 + T - 1, quantised append behind `seqlens`
+        (= p0) into kcache / vcache ((words, scales) each) through block_table.  attend = (k pages, v pages, lengths incl. the chunk, output rows): the pages
+        are expanded (dequant_cache_paged) and the chunk attends causally over them -- the reference's prefill attention step (cache/quant.py:83-117 +
+        flash_attn_with_kvcache; here exl3_attn_prefill.hip); attend = None: the attention core is left out and q stands in for its output.
+        Returns the rows o_proj reads (q may be a column range of the fused q|k|v output)."""
+        hd = self.shape.head_dim
+        rows = bsz * T
+        (kc, ks), (vc, vs) = kcache, vcache
+        qkv = type(L["q"]).forward_multi([L["q"], L["k"], L["v"]], xn) if hd == 128 else None
+        if qkv is not None:
+            # one GEMM for q|k|v; rope and the KV-cache append read its column ranges in place
+            q, k, v = qkv
+            ext.rope_strided(q, k, self.inv_freq, p0, None, None, 1.0, bsz, T)
+            ext.quant_cache_paged_strided(k, kc, ks, v, vc, vs, seqlens, block_table, self.page, T)
+        else:
+            q = L["q"].forward(xn).view(bsz, T, self.hq, hd)
+            k = L["k"].forward(xn).view(bsz, T, self.hkv, hd)
+            v = L["v"].forward(xn).view(bsz, T, self.hkv, hd)
+            ext.rope(q, q, k, k, self.inv_freq, p0, None, None, 2, 1.0)
+            ext.quant_cache_paged(k.view(bsz, T, -1), kc, ks, v.view(bsz, T, -1), vc, vs, seqlens, block_table, self.page, T)
+            q = q.view(rows, -1)
+        if attend is None:
+            return q
+        kd, vd, lens, ao = attend
+        ext.dequant_cache_paged(kc, ks, kd, vc, vs, vd, lens, block_table, self.page)
+        q2 = q if q.dim() == 2 else q.reshape(rows, -1)
+        q4 = q2.as_strided((bsz, T, self.hq, hd), (T * q2.stride(0), q2.stride(0), hd, 1), q2.storage_offset())
+        ext.attn_prefill_paged(q4, ao.view(bsz, T, self.hq, hd), kd.view(-1, self.page, self.hkv, hd), vd.view(-1, self.page, self.hkv, hd), block_table, lens)
+        return ao
+
     def prefill_chunk(self, tokens: int):
         """All linears + norms + rope + KV-quant of a `tokens`-token chunk (bsz 1); attention core out of scope.
         rows > 144 -> reconstruct_had_slice + hgemm (modules/quant/exl3.py:161-218)."""
@@ -1443,31 +1559,8 @@ class SyntheticEXL3Llama:
             ahead.begin()
         for L in self.layers:
             ext.rms_norm(x, L["norm1"], xn, self.eps)
-            qkv = type(L["q"]).forward_multi([L["q"], L["k"], L["v"]], xn) if hd == 128 else None
-            if qkv is not None:
-                # one GEMM for q|k|v; rope and the KV-cache append read its column ranges in place
-                q, k, v = qkv
-                ext.rope_strided(q, k, self.inv_freq, 0, None, None, 1.0, 1, tokens)
-                ext.quant_cache_paged_strided(k, self.pf_cache[0], self.pf_cache[2], v, self.pf_cache[1], self.pf_cache[3], self.pf_sl, self.pf_bt,
-                                              self.page, tokens)
-            else:
-                q = L["q"].forward(xn).view(1, tokens, self.hq, hd)
-                k = L["k"].forward(xn).view(1, tokens, self.hkv, hd)
-                v = L["v"].forward(xn).view(1, tokens, self.hkv, hd)
-                ext.rope(q, q, k, k, self.inv_freq, 0, None, None, 2, 1.0)
-                ext.quant_cache_paged(k.view(1, tokens, -1), self.pf_cache[0], self.pf_cache[2], v.view(1, tokens, -1), self.pf_cache[1],
-                                      self.pf_cache[3], self.pf_sl, self.pf_bt, self.page, tokens)
-                q = q.view(tokens, -1)
-            if self.prefill_attention:
-                # the reference's prefill attention step: dequantize the (just appended) pages, causal attention of the chunk over them
-                # (cache/quant.py:83-117 + flash_attn_with_kvcache; here exl3_attn_prefill.hip).  q may be a column range of the fused q|k|v output.
-                ext.dequant_cache_paged(self.pf_cache[0], self.pf_cache[2], self.pf_kd, self.pf_cache[1], self.pf_cache[3], self.pf_vd, self.pf_len,
-                                        self.pf_bt, self.page)
-                q2 = q if q.dim() == 2 else q.reshape(tokens, -1)
-                q4 = q2.as_strided((1, tokens, self.hq, hd), (tokens * q2.stride(0), q2.stride(0), hd, 1), q2.storage_offset())
-                ext.attn_prefill_paged(q4, self.pf_ao.view(1, tokens, self.hq, hd), self.pf_kd.view(-1, self.page, self.hkv, hd),
-                                       self.pf_vd.view(-1, self.page, self.hkv, hd), self.pf_bt, self.pf_len)
-                q = self.pf_ao
+            q = self._prefill_qkv_attend(L, xn, 1, tokens, 0, (self.pf_cache[0], self.pf_cache[2]), (self.pf_cache[1], self.pf_cache[3]), self.pf_sl, self.pf_bt,
+                                         (self.pf_kd, self.pf_vd, self.pf_len, self.pf_ao) if self.prefill_attention else None)
             if self.tp == 1:
                 L["o"].forward_add_residual(q, x)                           # residual add in the GEMM epilogue (q: attention output, or its stand-in)
                 ext.rms_norm(x, L["norm2"], xn, self.eps)

@@ -1,6 +1,6 @@
 """
 Device-side sampling (csrc/exl3_sampler.hip, csrc/exl3_logit_process.hip; include/exl3_hip.h: exl3_sample / exl3_gen_feed / exl3_gen_feed_stop /
-exl3_logit_process).
+exl3_embed_rows / exl3_logit_process).
 
 SamplerSettings collapses a (temperature, top-k, top-p, min-p) stack into the kernel's (mode, filters, ...) the way the reference collapses a sampler
 stack into its fused sampler (generator/sampler/custom.py:267-343): greedy when nothing can change the top token, a Gumbel sample of softmax(l / T)
@@ -143,6 +143,28 @@ def gen_feed(sampled, forced, embed: torch.Tensor, x0: torch.Tensor, tokens_out,
         if not (t.dtype == torch.int32 and t.is_contiguous() and t.device == x0.device and t.numel() >= n):
             raise RuntimeError("gen_feed: stop_ids / done [m] / live [1] must be contiguous int32 tensors on the device of x0")
     _check(_lib.lib().exl3_gen_feed_stop(*args, _p(stop_ids), stop_ids.numel(), _p(done), int(pad_token), _p(live), torch.cuda.current_stream(x0.device).cuda_stream))
+
+
+def embed_rows(ids: torch.Tensor, col0: int, T: int, embed: torch.Tensor, invalid: torch.Tensor, vocab: int | None = None, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The input rows of a prefill chunk: out[b * T + t] = embed[ids[b, col0 + t]] for the int32 id matrix `ids` [m, ld] (m <= 16) on the device -> fp16
+    [m * T, hidden].  An id outside [0, vocab) never indexes the table: its row is zeros and the sticky invalid[b] is set.  One launch (exl3_embed_rows),
+    graph-capturable when `out` is given."""
+    ok = (ids.is_cuda and ids.dtype == torch.int32 and ids.dim() == 2 and ids.is_contiguous() and embed.dtype == torch.half and embed.dim() == 2
+          and embed.is_contiguous() and embed.device == ids.device and invalid.dtype == torch.int32 and invalid.is_contiguous() and invalid.device == ids.device
+          and invalid.numel() >= ids.shape[0])
+    if not ok:
+        raise RuntimeError("embed_rows: contiguous int32 ids [m, ld] and invalid [m], fp16 embed [vocab, hidden], all on one GPU")
+    m, ld = ids.shape
+    hidden = embed.shape[1]
+    if out is None:
+        out = torch.empty((m * int(T), hidden), dtype=torch.half, device=ids.device)
+    if not (out.dtype == torch.half and out.is_contiguous() and out.device == ids.device and out.numel() == m * int(T) * hidden):
+        raise RuntimeError("embed_rows: out must be a contiguous fp16 [m * T, hidden] tensor on the ids' device")
+    if ids.device.index != torch.cuda.current_device():
+        torch.cuda.set_device(ids.device)
+    _check(_lib.lib().exl3_embed_rows(_p(ids), ld, int(col0), int(T), m, _p(embed), int(embed.shape[0] if vocab is None else vocab), hidden, _p(out), _p(invalid),
+                                      torch.cuda.current_stream(ids.device).cuda_stream))
+    return out
 
 
 MAX_STOP_IDS = 64

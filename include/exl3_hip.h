@@ -744,6 +744,13 @@ int exl3_gen_feed_stop(const int32_t* sampled, const int32_t* forced, int forced
                        int32_t* tokens_out, int out_len, int32_t* positions, int32_t* cache_seqlens, int32_t* attn_lens, int32_t* invalid, int64_t* step,
                        const int32_t* stop_ids, int n_stop, int32_t* done, int pad_token, int32_t* live, void* stream);
 
+/* exl3_embed_rows: the input rows of a prefill chunk straight from device-side token ids (the reference embeds on the host side of its generator).  ids is an
+ *   int32 matrix [m][ld_ids] (m = 1..16; the generation state's forced list), the chunk its columns [col0, col0 + T), T >= 1, inside it.
+ *   out[(b * T + t)][0 .. hidden) = embed[ids[b][col0 + t]] (both fp16, hidden a multiple of 8, 16-byte aligned, 16-byte copies).  The feed's rules hold for an id
+ *   outside [0, vocab): it never indexes the table, its row is written as zeros and invalid[b] is set (sticky: the entry never clears it).
+ *   One workgroup per output row.  Graph-capturable, allocates nothing, no workspace; no workgroup waits for another. */
+int exl3_embed_rows(const int32_t* ids, int ld_ids, int col0, int T, int m, const void* embed, int vocab, int hidden, void* out, int32_t* invalid, void* stream);
+
 /* ---- logit processors (exl3_logit_process.hip)    generator/rep_pen.cu (apply_rep_pens, apply_pres_freq_pens), generator/sampling_fused.cu:951-1020
  *      (apply_logit_bitmask), generator/sampler/custom.py:581-609 (LogitBias) -----------------------------------------------------------------------------
  * exl3_logit_process: one launch, rows r = 0 .. m - 1 (m = 1..16): logits_in [m][ld] (fp16, or fp32 when in_fp32) -> logits_out [m][ld] (fp16 / fp32 by out_fp32;

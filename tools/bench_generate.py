@@ -11,6 +11,13 @@
             calls; the replayed generation loop with processors on against the same loop without them (the two alternating), and generate() under a 256-token
             budget that stops at token ~20 (stop_token_ids) against the same call without stop ids (replays and wall time, capture included).
 
+  prompt    time to the first new token (from the call of generate(prompt, 1) until the sampled token is on the host: allocation, the uncaptured step, the
+            capture and the read included) with the prompt fed through the decode step token by token (prompt_mode "decode") against the prompt ingested through
+            the prefill route in chunks (prompt_mode "prefill"), the two modes alternating, at prompt lengths 8 .. 8192 on the 8B and 1B shapes; the prompt length
+            where prefill mode first wins; ingest_prompt alone (device time, tokens/s) over a chunk sweep at the longest prompt, from which the default chunk
+            (SyntheticEXL3Llama.gen_prefill_chunk) is taken; and the same ingestion with dequant_cache_paged switched off (timing only: the share of
+            re-expanding the past for every chunk and layer).
+
 Method: device events around whole windows that end in a synchronise, every shape warmed up, windows of at least --window seconds, the two sides of a comparison
 alternating in one process, min / median / max of the repeated windows reported.  A run without a GPU fails."""
 import argparse
@@ -254,13 +261,75 @@ def bench_generate_processors(dev, args, shape_name):
     return out
 
 
+def bench_prompt(dev, args, shape_name):
+    import torch
+    from exllamav3_amd import ext
+    from exllamav3_amd.llama_path import SHAPES, SyntheticEXL3Llama
+    lengths = [int(x) for x in args.prompt_lengths.split(",")]
+    chunks = [int(x) for x in args.prompt_chunks.split(",")]
+    m = SyntheticEXL3Llama(SHAPES[shape_name], K=4, cb=2, device=dev, kv_bits=4, layers=args.layers or None, max_ctx=(max(lengths) + 1 + 255) // 256 * 256)
+    gen = torch.Generator(); gen.manual_seed(3)
+    out = {"shape": shape_name, "layers": m.n_layers, "default_chunk": m.gen_prefill_chunk, "ttft_ms": {},
+           "method": "wall time of whole generate(prompt, 1) calls (ttft_ms), device time of ingest_prompt (ingest_chunk_sweep); one warm call, then %d windows of >= %.1f s per side, "
+                     "sides alternating" % (args.repeats, args.window)}
+
+    def windows(sides):
+        """sides: {name: callable} -> {name: spread of ms per call}: one warm call each (it sizes the window), then windows of >= args.window s, alternating."""
+        reps = {}
+        for name, fn in sides.items():
+            reps[name] = max(1, math.ceil(args.window * 1e3 / max(timed_window(fn, 1), 1e-3)))
+        res = {name: [] for name in sides}
+        for _ in range(args.repeats):
+            for name, fn in sides.items():
+                res[name].append(timed_window(fn, reps[name]) / reps[name])
+        return {name: dict(spread(v), unit="ms", calls_per_window=reps[name]) for name, v in res.items()}
+
+    m.generate(torch.randint(0, V, (8,), generator=gen), 1)                            # plans, the persistent step's first run
+    first_win = None
+    for P in lengths:
+        prompt = torch.randint(0, V, (P,), generator=gen)
+        r = windows({"decode": lambda: m.generate(prompt, 1), "prefill": lambda: m.generate(prompt, 1, prompt_mode="prefill")})
+        r["prefill_chunks"] = m.gen_stats.get("prefill_chunks")
+        r["speedup"] = round(r["decode"]["median"] / r["prefill"]["median"], 2)
+        for k in ("decode", "prefill"):
+            r[k]["prompt_tokens_per_s"] = round((P - 1) / (r[k]["median"] * 1e-3), 1)
+        if first_win is None and r["prefill"]["median"] < r["decode"]["median"]:
+            first_win = P
+        out["ttft_ms"][str(P)] = r
+        print("prompt", shape_name, P, json.dumps(r), flush=True)
+    out["prefill_first_wins_at"] = first_win
+    # ingestion alone over the chunk sweep at the longest prompt
+    P = max(lengths)
+    m.alloc_gen_state(1, 1, torch.randint(0, V, (1, P), generator=gen))
+    sweep = windows({str(c): (lambda c=c: m.ingest_prompt(P - 1, c)) for c in chunks})
+    for c, v in sweep.items():
+        v["tokens_per_s"] = round((P - 1) / (v["median"] * 1e-3), 1)
+    out["ingest_chunk_sweep"] = dict(sweep, prompt_tokens=P - 1)
+    best = min(sweep, key=lambda c: sweep[c]["median"])
+    out["best_chunk"] = int(best)
+    real = ext.dequant_cache_paged
+    try:
+        ext.dequant_cache_paged = lambda *a, **k: None                                # timing only: the attention then reads stale pages
+        off = windows({"no_dequant": lambda: m.ingest_prompt(P - 1, int(best))})["no_dequant"]
+    finally:
+        ext.dequant_cache_paged = real
+    out["dequant_cache_paged_share"] = round(1.0 - off["median"] / sweep[best]["median"], 4)
+    out["ingest_without_dequant_ms"] = off
+    print("prompt", shape_name, json.dumps({k: out[k] for k in ("prefill_first_wins_at", "ingest_chunk_sweep", "best_chunk", "dequant_cache_paged_share")}), flush=True)
+    del m
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window (at least)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--new-tokens", type=int, default=256)
     ap.add_argument("--layers", type=int, default=0, help="debug: fewer layers (invalidates the number)")
-    ap.add_argument("--skip", default="", help="comma list of: sampler, 8b, 1b, processors (a skipped section keeps what --out already holds)")
+    ap.add_argument("--skip", default="", help="comma list of: sampler, 8b, 1b, processors, prompt (a skipped section keeps what --out already holds)")
+    ap.add_argument("--prompt-lengths", default="8,64,512,2048,8192", help="section prompt: prompt lengths")
+    ap.add_argument("--prompt-chunks", default="512,1024,2048,4096", help="section prompt: the chunk sweep of ingest_prompt")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generate_bench.json"))
     args = ap.parse_args()
     import torch
@@ -286,6 +355,8 @@ def main():
     if "processors" not in skip:
         res["logit_process_us_per_call"] = bench_logit_process(dev, args)
         res["generate_processors"] = {shape: bench_generate_processors(dev, args, shape) for shape in ("llama-3.1-8b", "llama-3.2-1b")}
+    if "prompt" not in skip:
+        res["prompt"] = {shape: bench_prompt(dev, args, shape) for shape in ("llama-3.1-8b", "llama-3.2-1b")}
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
