@@ -241,3 +241,4 @@ def _declare(l):
     sig("exl3_set_gemm3_cpw", i32)
     sig("exl3_set_attn_wide_waves", i32)
     sig("exl3_set_gemv_defer_wg_per_cu", i32)
+    sig("exl3_gemv_plan", i32, ctypes.POINTER(i32), i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int32), i32, ctypes.POINTER(i32))

@@ -130,7 +130,8 @@ __global__ void mgemm_slot_reduce_kernel(void* C, int c_fp32, int num_tokens, in
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host side
+// Host side: every entry point fills a GemvCall; gemv_run validates it, plans each pass (gemv_plan_pass: pure, also behind the device-free
+// exl3_gemv_plan query that tests/test_gemv_plan.py replays), fills the GemvArgs and launches.
 // ------------------------------------------------------------------------------------------------
 
 static int g_gemv_variant = -1;      // -1: read EXL3_HIP_GEMV_VARIANT (default 1 = FAST)
@@ -179,21 +180,11 @@ extern "C" int exl3_set_gemm3_min_rows(int v) { g_gemm3_min_rows = v; return EXL
 static int g_gemm3_cpw = -1;
 static int gemm3_cpw() { if (g_gemm3_cpw < 0) { const char* e = getenv("EXL3_HIP_GEMM3_CPW"); const int v = e ? atoi(e) : 0; g_gemm3_cpw = (v == 1 || v == 2 || v == 4) ? v : 0; } return g_gemm3_cpw; }
 extern "C" int exl3_set_gemm3_cpw(int v) { g_gemm3_cpw = (v == 1 || v == 2 || v == 4) ? v : 0; return EXL3_OK; }
-static int gemm3_max_waves(int K, int mt, int rot)
-{
-    switch (K)
-    {
-        case 1: return exl3_gemm3_max_waves_k1(mt, rot); case 2: return exl3_gemm3_max_waves_k2(mt, rot); case 3: return exl3_gemm3_max_waves_k3(mt, rot);
-        case 4: return exl3_gemm3_max_waves_k4(mt, rot); case 5: return exl3_gemm3_max_waves_k5(mt, rot); case 6: return exl3_gemm3_max_waves_k6(mt, rot);
-        case 7: return exl3_gemm3_max_waves_k7(mt, rot); default: return exl3_gemm3_max_waves_k8(mt, rot);
-    }
-}
 // LDS a generation-3 workgroup may use: one 16-wave workgroup per CU, two 8-wave ones, four of 4 waves (160 KB per CU, some left for the runtime)
 static int gemm3_lds_budget(int cpw3) { return cpw3 == 4 ? 139264 : (cpw3 == 2 ? 73728 : 36864); }
-static int gemm3_chunk_blocks(int mp, int cpw3, int bps)
+static int gemm3_chunk_blocks(int mp, int cpw3, int bps, int chunk_bytes)
 {
-    static const int chunk_bytes_env = [] { const char* e = getenv("EXL3_HIP_GEMM3_CHUNK_BYTES"); return e ? atoi(e) : 0; }();
-    const int budget = chunk_bytes_env > 0 ? chunk_bytes_env : gemm3_lds_budget(cpw3);
+    const int budget = chunk_bytes > 0 ? chunk_bytes : gemm3_lds_budget(cpw3);
     int chunk = (budget / (mp * 2) - 16) / 128;
     if (chunk > 16 * cpw3) chunk = 16 * cpw3;                // the rotated-input copy maps a chunk row onto <= 64 x waves 16-byte pieces (16 per block)
     if (chunk > 32) chunk = 32;
@@ -225,7 +216,6 @@ static double gemm3_cost(int groups, int cpw3, int s, int b, int cus, bool defer
 extern "C" int exl3_set_gemv_defer_wg_per_cu(int v) { g_gemv_defer_wg_per_cu = v; return EXL3_OK; }
 extern "C" int exl3_set_gemv_max_waves(int v) { g_gemv_nwv = v; return EXL3_OK; }
 
-
 // generation 4 (exl3_gemv4.kspec.hip) takes the 1..4-row launches it supports (plain / rotated / RMSNorm / silu-mul input, final or deferred
 // output, slices of at most 32 Hadamard blocks); 0 pins generation 2 (A/B runs, the bit-identity tests between generation-2 pipelines)
 static int g_gemv_gen4 = -1;
@@ -236,9 +226,9 @@ static int gemv_gen4()
 }
 extern "C" int exl3_set_gemv_gen4(int v) { g_gemv_gen4 = v ? 1 : 0; return EXL3_OK; }
 
-// fx pipeline: exl3_fx_zero_next(ptr, bytes) asks the NEXT run_mgemm call OF THIS THREAD ON THIS DEVICE to clear a buffer as a side job (the gate / up
+// fx pipeline: exl3_fx_zero_next(ptr, bytes) asks the NEXT dispatcher call OF THIS THREAD ON THIS DEVICE to clear a buffer as a side job (the gate / up
 // accumulators, cleared by the o_proj launch in front of the gate|up launch that adds into them).  The request is one-shot and never outlives that
-// call: run_mgemm takes it on entry (take_fx_zero), so an argument error, a launch that is not a plain generation-4 launch, or a launch on another
+// call: gemv_run takes it on entry (take_fx_zero), so an argument error, a launch that is not a plain generation-4 launch, or a launch on another
 // device fails loudly ("cannot clear") instead of leaving the pointer armed for an unrelated later launch.
 struct FxZeroReq { void* ptr; int64_t bytes; int device; };
 static thread_local FxZeroReq g_fx_zero = { nullptr, 0, -1 };
@@ -264,53 +254,99 @@ static int gemv_variant()
     }
     return g_gemv_variant;
 }
-
 extern "C" int exl3_set_gemv_variant(int v) { g_gemv_variant = v ? 1 : 0; return EXL3_OK; }
 
-static int choose_split(int gen, int total_colblocks, int k, int m, int num_cus, int force_split)
+// The knobs as ONE call sees them: snapshotted at the top of the call (and of the plan query), so the planner never reads the globals
+struct GemvTuning { int variant, max_waves, defer_wg_per_cu, gemm3_min_rows, gemm3_cpw, gen4, tail_xcd_local, gemm3_chunk_bytes; };
+static GemvTuning gemv_tuning()
+{
+    static const int chunk_bytes_env = [] { const char* e = getenv("EXL3_HIP_GEMM3_CHUNK_BYTES"); return e ? atoi(e) : 0; }();
+    GemvTuning t;
+    t.variant = gemv_variant(); t.max_waves = g_gemv_nwv; t.defer_wg_per_cu = g_gemv_defer_wg_per_cu; t.gemm3_min_rows = g_gemm3_min_rows;
+    t.gemm3_cpw = gemm3_cpw(); t.gen4 = gemv_gen4(); t.tail_xcd_local = g_tail_xcd_local; t.gemm3_chunk_bytes = chunk_bytes_env;
+    return t;
+}
+
+// The per-K translation units' entry points, indexed by K - 1
+#define GEMV_PER_K(f) { f##1, f##2, f##3, f##4, f##5, f##6, f##7, f##8 }
+typedef void (*GemvLaunchFn)(int, int, int, int, dim3, size_t, hipStream_t, const GemvArgs&);
+static const GemvLaunchFn g_launch_gen2[8] = GEMV_PER_K(exl3_gemv2_launch_k);      // (cb, var, ng, nwv, ...)
+static const GemvLaunchFn g_launch_gen3[8] = GEMV_PER_K(exl3_gemm3_launch_k);      // (cb, mt, var, nwt, ...)
+static const GemvLaunchFn g_launch_gen4[8] = GEMV_PER_K(exl3_gemv4_launch_k);      // (cb, var, mode, nwv, ...)
+static int (* const g_gemm3_max_waves[8])(int mt, int rot) = GEMV_PER_K(exl3_gemm3_max_waves_k);
+#undef GEMV_PER_K
+
+// generations 2 and 4: the requested split (fs > 0) or generation 2's own rule, normalised so that no slice is empty
+static int choose_split(int total_colblocks, int k, int num_cus, int fs)
 {
     const int nb = k / 128;
     int S;
-    if (force_split > 0) S = force_split;
-    else if (gen == 3)
-    {
-        // gen 3: 4-wave workgroups, four resident per CU (LDS / registers); fill those slots, slices of at least 4 Hadamard blocks (shorter
-        // slices lose more to the reduce launch and the per-workgroup prologue than they gain: tools/bench_gemm3.py, 4096 x 4096)
-        // (PMC on gate|up at 16 rows with S = 1: 224 workgroups = one wave per SIMD, VALU active 29 % of the kernel)
-        S = (4 * num_cus + total_colblocks / 2) / total_colblocks;
-        int maxS = nb / 4; if (maxS < 1) maxS = 1;
-        if (S > maxS) S = maxS;
-        const long ws_cap = (long) (EXL3_WS_REGION_BYTES / ((long) total_colblocks * m * 512));      // the slabs must fit one workspace region
-        if (S > ws_cap) S = ws_cap < 1 ? 1 : (int) ws_cap;
-    }
-    else
-    {
-        // gen 2: a workgroup is up to 16 waves that split its k-slice, so one workgroup per CU already fills the CU.
-        // Split k across workgroups only until every CU has one (no reduce launch when the column blocks suffice).
-        if (4 * total_colblocks >= 3 * num_cus) S = 1;
-        else S = (num_cus + total_colblocks - 1) / total_colblocks;
-    }
+    if (fs > 0) S = fs;
+    // gen 2: a workgroup is up to 16 waves that split its k-slice, so one workgroup per CU already fills the CU.
+    // Split k across workgroups only until every CU has one (no reduce launch when the column blocks suffice).
+    else if (4 * total_colblocks >= 3 * num_cus) S = 1;
+    else S = (num_cus + total_colblocks - 1) / total_colblocks;
     if (S < 1) S = 1;
     if (S > nb) S = nb;
-    int blocks_per_slice = (nb + S - 1) / S;
-    // normalise S so that no slice is empty
-    S = (nb + blocks_per_slice - 1) / blocks_per_slice;
-    return S;
+    const int blocks_per_slice = (nb + S - 1) / S;
+    return (nb + blocks_per_slice - 1) / blocks_per_slice;
 }
 
 // GEMV_IN_RESID operands: the producer linear's deferred slabs + svh, and where the workgroups of column block 0 publish the new residual
 struct GemvResidIn { const float* slab; int S; const void* svh; void* resid_out; float* ss_out; };
 
-static int run_mgemm(const void* A, const void* const* Bs, void* const* Cs, const void* const* suhs, const void* const* svhs,
-                     const void* const* biases, const int* ns, int count, int m, int k, int K, int cb, int c_fp32,
-                     int force_split, hipStream_t st, int flags = 0, const void* const* xhs = nullptr, const float* const* xsums = nullptr,
-                     float** slabs_out = nullptr, int* S_out = nullptr, const GemvEpi* epi = nullptr,
-                     const void* norm_w = nullptr, const float* ss_part = nullptr, float eps = 0.0f, const GemvTable* tbl = nullptr,
-                     const float* act_g = nullptr, const float* act_u = nullptr, int act_S = 0, const void* act_svh_g = nullptr,
-                     const void* act_svh_u = nullptr, const GemvResidIn* rsd = nullptr, const GemvRescale* act_rs = nullptr, int cpw = 0,
-                     float* fx_ss_out = nullptr, const GemvAttm* attm = nullptr, const GemvQkvm* qkvm = nullptr)
+// One request to the dispatcher.  Entry points zero-initialise it (GemvCall c = {}) and assign the fields they use.
+struct GemvCall
 {
-    FxZeroReq fxz = take_fx_zero();          // one-shot: whatever happens below, the request does not survive this call
+    const void* A; const void* const* Bs; void* const* Cs; const void* const* suhs; const void* const* svhs; const void* const* biases;
+    const int* ns; int count, m, k, K, cb, c_fp32, force_split, flags;
+    const void* const* xhs; const float* const* xsums;          // GEMV_IN_ROTATED
+    float** slabs_out; int* S_out;
+    const GemvEpi* epi; const GemvTable* tbl; const GemvResidIn* rsd; const GemvRescale* act_rs; const GemvAttm* attm; const GemvQkvm* qkvm;
+    const void* norm_w; const float* ss_part; float eps;        // GEMV_IN_NORM
+    const float* act_g; const float* act_u; int act_S; const void* act_svh_g; const void* act_svh_u;      // GEMV_IN_ACT / GEMV_IN_ACTFX
+    int cpw;                    // > 0: wave-per-column-block layout (exl3_gemv2.kspec.hip): cpw column blocks of one matrix per workgroup, one wave each
+    float* fx_ss_out;           // GEMV_IN_FX
+    hipStream_t stream;
+};
+
+// What gemv_validate keeps of a request for the planner: sizes, modes and which operands are there -- no device pointer
+struct GemvShape
+{
+    int flags;                  // the request's flags and those its operand blocks imply
+    int count, m, k, K, cb, force_split, cpw, total_cb, epi_mode;
+    const int* ns;
+    bool deferred /* slabs or atomic adds: nothing to reduce */, atomic_out, rotated, in_norm, in_act, in_fx;
+    bool tbl, tbl_gen2 /* fp16 act input / per-matrix widths: generation 2's */, rsd, attm, qkvm, xsums /* every matrix has its block sums */, fx_zero;
+};
+
+// What one pass launches: one int32 record of exl3_gemv_plan, in this order
+struct GemvPlan
+{
+    int rows;                   // rows of the pass
+    int gen;                    // kernel generation 2 | 3 | 4
+    int sel;                    // its instantiation: generation 4 mode 0..9, generation 2 ng (rows / 4: 1 | 2 | 4), generation 3 mt (row tiles: 1 | 2 | 4)
+    int pre_xh;                 // generation 3: the activations are rotated once in front of the launch
+    int S, bps;                 // k-slices, Hadamard blocks per slice
+    int nwv;                    // waves per workgroup
+    int chunk_blocks;           // generations 2, 3: Hadamard blocks of activations in LDS at a time
+    int cpw;                    // column blocks per workgroup: the wave-per-column-block layout's, generation 3's; 0 otherwise
+    int grid_x, grid_y, grid_z, lds;
+    int ws_floats;              // slab (+ tail epilogue) floats of the pass in the workspace region
+    int rows_per_pass, xcd_local;      // GemvEpi
+    int reduce;                 // the split-k reduce launch follows
+};
+static_assert(sizeof(GemvPlan) == EXL3_GEMV_PLAN_INTS * 4, "GemvPlan is the record of exl3_gemv_plan");
+
+static int gemv_validate(const GemvCall& c, bool fx_zero, GemvShape& s)
+{
+    const void* A = c.A; const void* const* Bs = c.Bs; void* const* Cs = c.Cs; const void* const* suhs = c.suhs; const void* const* svhs = c.svhs;
+    const int* ns = c.ns; const int count = c.count, m = c.m, k = c.k, K = c.K, cb = c.cb, cpw = c.cpw, act_S = c.act_S;
+    const void* const* xhs = c.xhs; const float* const* xsums = c.xsums; const void* norm_w = c.norm_w; const float* ss_part = c.ss_part;
+    const GemvEpi* epi = c.epi; const GemvTable* tbl = c.tbl; const GemvResidIn* rsd = c.rsd; const GemvAttm* attm = c.attm; const GemvQkvm* qkvm = c.qkvm;
+    const float* act_g = c.act_g; const float* act_u = c.act_u; const void* act_svh_g = c.act_svh_g; const void* act_svh_u = c.act_svh_u;
+    float* fx_ss_out = c.fx_ss_out;
+    int flags = c.flags;
     if (rsd) flags |= GEMV_IN_RESID;
     // cpw > 0: wave-per-column-block layout (exl3_gemv2.kspec.hip): cpw column blocks of one matrix per workgroup, one wave each
     EXL3_CHECK_ARG(cpw >= 0 && cpw <= 16, "exl3_gemv_ex: column blocks per workgroup must be in [0, 16]");
@@ -338,7 +374,6 @@ static int run_mgemm(const void* A, const void* const* Bs, void* const* Cs, cons
     EXL3_CHECK_ARG(!in_fx || ((flags & GEMV_IN_NORM) && m <= 4 && fx_ss_out), "exl3_gemv_ex_fx: needs GEMV_IN_NORM, m <= 4 and ss_out");
     const bool deferred = (flags & (GEMV_OUT_DEFERRED | GEMV_OUT_ATOMIC)) != 0, rotated = (flags & GEMV_IN_ROTATED) != 0;
     EXL3_CHECK_ARG(!(deferred || rotated) || m <= 16, "exl3_gemv_ex: at most 16 rows");
-    const int epi_sets = !epi ? 0 : (epi->mode == GEMV_EPI_ACT ? 2 : 1);
     EXL3_CHECK_ARG(!rotated || xhs, "exl3_gemv_ex: rotated input requires xh pointers");
     const bool in_norm = (flags & GEMV_IN_NORM) != 0;
     EXL3_CHECK_ARG(!in_norm || (norm_w && ss_part && !rotated && m <= 16), "exl3_gemv_ex: GEMV_IN_NORM needs norm_w, ss_part, raw input and m <= 16");
@@ -355,6 +390,7 @@ static int run_mgemm(const void* A, const void* const* Bs, void* const* Cs, cons
     EXL3_CHECK_ARG(!rsd || (in_norm && deferred && m <= 4 && rsd->slab && rsd->S >= 1 && rsd->svh && rsd->resid_out && rsd->ss_out && rsd->resid_out != A),
                    "exl3_gemv_ex_resid: needs GEMV_IN_NORM, deferred output, m <= 4, producer slabs + svh and a resid_out buffer other than resid_in");
     int total_cb = 0;
+    bool has_xsums = xsums != nullptr;
     if (tbl)
     {
         EXL3_CHECK_ARG(ns[0] % 128 == 0 && ns[0] > 0, "exl3_gemm: n must be divisible by 128");
@@ -366,356 +402,384 @@ static int run_mgemm(const void* A, const void* const* Bs, void* const* Cs, cons
         EXL3_CHECK_ARG(Bs[i] && (deferred || (Cs && Cs[i] && svhs && svhs[i])) && (rotated || (suhs && suhs[i])), "exl3_gemm: null pointer");
         EXL3_CHECK_ARG(!atomic_out || (Cs[i] && svhs[i]), "exl3_gemv_ex: GEMV_OUT_ATOMIC needs an accumulator and svh per matrix");
         total_cb += ns[i] / 128;
+        if (has_xsums && !xsums[i]) has_xsums = false;
     }
-    Exl3DevCtx* ctx = exl3_get_ctx(st);
-    if (!ctx) return EXL3_ERR_INIT;
+    s.flags = flags; s.count = count; s.m = m; s.k = k; s.K = K; s.cb = cb; s.force_split = c.force_split; s.cpw = cpw; s.total_cb = total_cb;
+    s.epi_mode = epi ? epi->mode : GEMV_EPI_NONE; s.ns = ns;
+    s.deferred = deferred; s.atomic_out = atomic_out; s.rotated = rotated; s.in_norm = in_norm; s.in_act = in_act; s.in_fx = in_fx;
+    s.tbl = tbl != nullptr; s.tbl_gen2 = tbl && (tbl->act_u || tbl->n_list); s.rsd = rsd != nullptr; s.attm = attm != nullptr; s.qkvm = qkvm != nullptr;
+    s.xsums = has_xsums; s.fx_zero = fx_zero;
+    return EXL3_OK;
+}
 
-    const int var = gemv_variant();
-    // generation 3 streams the weights once per up to 64 rows (exl3_gemm3.kspec.hip); the special input / output modes stay on generation 2
-    const bool g3_ok = g_gemm3_min_rows > 0 && !in_norm && !tbl && !in_act && !epi && true;
-    const int pass_rows = (g3_ok && !deferred && !rotated && m > 16) ? (m > 32 ? 64 : 32) : 16;
-    for (int m0 = 0; m0 < m; m0 += pass_rows)
+// generation 3 streams the weights once per up to 64 rows (exl3_gemm3.kspec.hip); the special input / output modes stay on generation 2
+static bool gemm3_admits(const GemvShape& s, const GemvTuning& t) { return t.gemm3_min_rows > 0 && !s.in_norm && !s.tbl && !s.in_act && s.epi_mode == GEMV_EPI_NONE; }
+static int gemv_pass_rows(const GemvShape& s, const GemvTuning& t) { return (gemm3_admits(s, t) && !s.deferred && !s.rotated && s.m > 16) ? (s.m > 32 ? 64 : 32) : 16; }
+
+// generation 3: the cheapest normalised split (no empty slice) by the cost model, for `groups` workgroup columns of cpw3 column blocks each
+static int gemm3_cost_split(const GemvShape& s, int mp, int cus, int cpw3, int groups)
+{
+    const int nbk = s.k / 128;
+    int forced_S = 0;
+    if (s.force_split > 0)
     {
-        const int mp = (m - m0) < pass_rows ? (m - m0) : pass_rows;
-        GemvArgs args;
-        memset((void*) &args, 0, sizeof(args));
-        // measured in the fused pipeline (tools/prof_tail.py, Llama-3.1-8B shapes): generation 3 is ahead from 5 rows with rotated input; with raw
-        // input its 8 half-waves per workgroup would spend longer on the input Hadamards than generation 2's 16..32, so it starts at 9 rows
-        // and, for wide launches, rotates the activations ONCE first (the role of the reference's A_had temporary, "storage for input transform": quant/exl3_gemm.cu:30, 139-145)
-        const bool g3 = cpw == 0 && g3_ok && mp >= (rotated ? g_gemm3_min_rows : (g_gemm3_min_rows > 9 ? g_gemm3_min_rows : 9));
-        const int gen = (cpw == 0 && g3) ? 3 : 2;
-        int pass_flags = flags;
-        const void* pre_xh[GEMV_MAX_MATS] = { nullptr };
-        const size_t xh_bytes = (size_t) mp * k * 2;
-        if (g3 && !rotated && (long) total_cb * mp >= 1024 && xh_bytes * count <= (size_t) EXL3_WS_XH_BYTES)
-        {
-            char* xh0 = (char*) ctx->workspace + EXL3_WS_XH_OFFSET;
-            for (int i = 0; i < count; ++i)
-            {
-                // identical suh -> one rotation serves both (gate / up of some checkpoints share it; cheap pointer test)
-                int same = -1;
-                for (int j = 0; j < i; ++j) if (suhs[j] == suhs[i]) { same = j; break; }
-                if (same >= 0) { pre_xh[i] = pre_xh[same]; continue; }
-                void* dst = xh0 + (size_t) i * xh_bytes;
-                int rc = exl3_had_r_128((const half_t*) A + (size_t) m0 * k, dst, suhs[i], nullptr, 1.0f, mp, k, 0, st);
-                if (rc != EXL3_OK) return rc;
-                pre_xh[i] = dst;
-            }
-            pass_flags |= GEMV_IN_ROTATED;
-        }
-        // generation 3: column blocks per workgroup and the split are chosen together (16-row passes; 32- / 64-row passes keep 4-wave workgroups)
-        int g3cpw = 1, g3fs = 0;
-        if (g3)
-        {
-            const int mt_ = mp > 32 ? 4 : (mp > 16 ? 2 : 1);
-            const int maxw = gemm3_max_waves(K, mt_, (pass_flags & GEMV_IN_ROTATED) ? 1 : 0);
-            const int nbk = k / 128, cus = ctx->num_cus;
-            int forced_S = 0;
-            if (force_split > 0)
-            {
-                const int fsq = force_split > nbk ? nbk : (force_split > 64 ? 64 : force_split);        // (the search below stops at 64 slices)
-                const int fb = (nbk + fsq - 1) / fsq; forced_S = (nbk + fb - 1) / fb;
-            }
-            double best = 1e30;
-            // two column blocks per workgroup wherever the instantiation's register budget allows 8 waves (measured best in the whole step; one block
-            // otherwise; four only on request: exl3_set_gemm3_cpw / EXL3_HIP_GEMM3_CPW) -- the split then follows the cost model for that choice
-            const int c3_want = (gemm3_cpw() && 4 * gemm3_cpw() <= maxw) ? gemm3_cpw() : (maxw >= 8 ? 2 : 1);
-            for (int c3 = c3_want; c3 <= c3_want; ++c3)
-            {
-                int groups = 0;
-                for (int i = 0; i < count; ++i) groups += (ns[i] / 128 + c3 - 1) / c3;
-                for (int s_ = 1; s_ <= nbk && s_ <= 64; ++s_)
-                {
-                    const int b = (nbk + s_ - 1) / s_;
-                    if ((nbk + b - 1) / b != s_) continue;          // not a normalised split
-                    if (forced_S > 0 && s_ != forced_S) continue;
-                    // the slabs must fit one workspace region -- a launch that writes none (one slice, finished output) always fits (with
-                    // every candidate rejected the split stayed 0 and the slice length below divided by it: lm_head-sized n at 33..64 rows)
-                    if ((s_ > 1 || deferred) && (long) total_cb * s_ * mp * 512 > (long) EXL3_WS_REGION_BYTES) continue;
-                    const double c = gemm3_cost(groups, c3, s_, b, cus, deferred);
-                    if (c < best) { best = c; g3cpw = c3; g3fs = s_; }
-                }
-            }
-            if (g3fs < 1) { g3fs = 1; g3cpw = c3_want; }            // (forced split that is not normalised / nothing fits: one slice)
-        }
-        args.act_g = act_g; args.act_u = act_u; args.act_S = act_S;
-        args.act_svh_g = (const half_t*) act_svh_g; args.act_svh_u = (const half_t*) act_svh_u;
-        args.norm_w = (const half_t*) norm_w; args.ss_part = ss_part; args.eps = eps;
-        if (in_fx) args.rs_ss_out = fx_ss_out;
-        if (rsd) { args.rs_slab = rsd->slab; args.rs_S = rsd->S; args.rs_svh = (const half_t*) rsd->svh; args.rs_resid_out = (half_t*) rsd->resid_out; args.rs_ss_out = rsd->ss_out; }
-        if (act_rs) args.act_rs = *act_rs;
-        if (attm) { args.attm = *attm; args.attm.magic_gq = gemv_magic((uint32_t) attm->gq); }
-        if (qkvm) args.qkvm = *qkvm;
-        int fs = force_split;
-        if (g3) fs = g3fs;
-        else if (deferred && fs == 0)
-        {
-            // deferred epilogue: the reduction is free (a glue kernel / tail epilogue does it), so pick the split that balances the
-            // chip.  All workgroups of these launches are resident at once and the kernel is VALU-bound per CU, so the launch
-            // takes as long as the busiest CU: ceil(workgroups / CUs) * blocks per workgroup.  Fewest slabs among the minima;
-            // a light preference for >= 2 workgroups per CU (tools/sweep_split.py: gate/up 3 -> 8 is -3 us per layer).
-            const int nbk = k / 128, cus = ctx->num_cus;
-            double best_cost = 1e30;
-            fs = 1;
-            for (int s = 1; s <= nbk && s <= 64; ++s)
-            {
-                const int b = (nbk + s - 1) / s;
-                if ((nbk + b - 1) / b != s) continue;              // not a normalised split
-                const long wg = (long) total_cb * s;
-                const double cost = (double) ((wg + cus - 1) / cus) * b + (wg < 2l * cus ? 0.25 : 0.0) + 1e-3 * s;
-                if (cost < best_cost) { best_cost = cost; fs = s; }
-            }
-            if (g_gemv_defer_wg_per_cu > 0) fs = (g_gemv_defer_wg_per_cu * ctx->num_cus + total_cb - 1) / total_cb;
-            if (fs < 1) fs = 1;
-            if (epi && fs > 64) fs = 64;                         // tail epilogue: one pass of slabs must fit the workgroup LDS
-        }
-        int total_groups = 0;
+        const int fsq = s.force_split > nbk ? nbk : (s.force_split > 64 ? 64 : s.force_split);        // (the search below stops at 64 slices)
+        const int fb = (nbk + fsq - 1) / fsq; forced_S = (nbk + fb - 1) / fb;
+    }
+    double best = 1e30;
+    int S = 1;                                              // (forced split that is not normalised / nothing fits: one slice)
+    for (int s_ = 1; s_ <= nbk && s_ <= 64; ++s_)
+    {
+        const int b = (nbk + s_ - 1) / s_;
+        if ((nbk + b - 1) / b != s_) continue;          // not a normalised split
+        if (forced_S > 0 && s_ != forced_S) continue;
+        // the slabs must fit one workspace region -- a launch that writes none (one slice, finished output) always fits (with
+        // every candidate rejected the split stayed 0 and the slice length below divided by it: lm_head-sized n at 33..64 rows)
+        if ((s_ > 1 || s.deferred) && (long) s.total_cb * s_ * mp * 512 > (long) EXL3_WS_REGION_BYTES) continue;
+        const double c = gemm3_cost(groups, cpw3, s_, b, cus, s.deferred);
+        if (c < best) { best = c; S = s_; }
+    }
+    return S;
+}
+// deferred epilogue: the reduction is free (a glue kernel / tail epilogue does it), so pick the split that balances the
+// chip.  All workgroups of these launches are resident at once and the kernel is VALU-bound per CU, so the launch
+// takes as long as the busiest CU: ceil(workgroups / CUs) * blocks per workgroup.  Fewest slabs among the minima;
+// a light preference for >= 2 workgroups per CU (tools/sweep_split.py: gate/up 3 -> 8 is -3 us per layer).
+static int deferred_balance_split(const GemvShape& s, int cus, const GemvTuning& t)
+{
+    const int nbk = s.k / 128;
+    double best_cost = 1e30;
+    int fs = 1;
+    for (int sp = 1; sp <= nbk && sp <= 64; ++sp)
+    {
+        const int b = (nbk + sp - 1) / sp;
+        if ((nbk + b - 1) / b != sp) continue;              // not a normalised split
+        const long wg = (long) s.total_cb * sp;
+        const double cost = (double) ((wg + cus - 1) / cus) * b + (wg < 2l * cus ? 0.25 : 0.0) + 1e-3 * sp;
+        if (cost < best_cost) { best_cost = cost; fs = sp; }
+    }
+    if (t.defer_wg_per_cu > 0) fs = (t.defer_wg_per_cu * cus + s.total_cb - 1) / s.total_cb;
+    if (fs < 1) fs = 1;
+    if (s.epi_mode != GEMV_EPI_NONE && fs > 64) fs = 64;     // tail epilogue: one pass of slabs must fit the workgroup LDS
+    return fs;
+}
+// waves per workgroup, generation 4: generation 2's measured choices (below) within 8 waves
+static int gemv4_waves(int bps, bool deferred, int max_waves)
+{
+    int nwv = 8;
+    if (nwv > (bps > 4 ? bps : 4)) nwv = bps > 4 ? bps : 4;
+    if (deferred && nwv > 4 && bps <= 16) nwv = 4;
+    if (max_waves < 0) nwv = -max_waves < 8 ? -max_waves : 8;
+    if (nwv > bps * 4) nwv = bps * 4;
+    if (max_waves > 0 && nwv > max_waves) nwv = max_waves;
+    return nwv < 1 ? 1 : nwv;
+}
+// waves per workgroup, generation 2 (classic layout; the wave-per-column-block layout has one wave per column block of the group)
+static int gemv2_waves(const GemvShape& s, int ng, int bps, int max_waves)
+{
+    int nwv = 16 / ng;                                   // partial-sum LDS: nwv * 4*ng rows * 512 B <= 32 KB
+    const int units = bps * (8 / G2_PF);                 // the waves split the slice's tile rows in units of G2_PF
+    // measured on MI355X (tools/prof_tail.py, batch 1): one wave per Hadamard block of the slice, but at least 4 waves --
+    // more waves than that do not help (the kernel is VALU / fixed-latency bound), fewer starve the short slices
+    if (nwv > (bps > 4 ? bps : 4)) nwv = bps > 4 ? bps : 4;
+    // deferred launches keep every workgroup resident (balanced split above): 4 waves = one per SIMD per workgroup with equal
+    // rows each, so no SIMD ends up with an extra wave (tools/gemv_timeline.py: down_proj's 7-wave workgroups left a
+    // 4/4/3/3 SIMD load and a 1.8 us wait at the workgroup barrier)
+    if (s.deferred && nwv > 4 && bps <= 16) nwv = 4;
+    // variants above 64 VGPRs (3INST/MCG decode, NORM prep, K >= 5 rings) fit 7 or 6 waves per SIMD: three 8-wave workgroups per
+    // CU instead of one 16-wave workgroup (tools/bench_lmhead.py: lm_head 3INST 105 -> 87 us, NORM 92 -> 81 us)
+    if (!s.deferred && ng == 1 && (s.cb != 2 || s.tbl || s.K >= 5) && nwv > 8) nwv = 8;
+    if (max_waves < 0) nwv = (-max_waves < 16 / ng) ? -max_waves : 16 / ng;      // tuning: forced wave count
+    if (s.in_act && nwv > 4) nwv = 4;                    // (classic layout) ACT-mode kernels are built for 4-wave workgroups (256 VGPRs available)
+    if (nwv > units) nwv = units;
+    if (max_waves > 0 && nwv > max_waves) nwv = max_waves;
+    return nwv < 1 ? 1 : nwv;
+}
+
+// Everything one pass of mp rows launches on a chip of num_cus CUs.  Pure: no HIP call, no context, no pointer is followed but s.ns.
+static int gemv_plan_pass(const GemvShape& s, int mp, int num_cus, const GemvTuning& t, GemvPlan& p)
+{
+    memset((void*) &p, 0, sizeof(p));
+    const int k = s.k, nb = k / 128, cpw = s.cpw, count = s.count, var = t.variant;
+    const bool epi = s.epi_mode != GEMV_EPI_NONE;
+    p.rows = mp;
+    // measured in the fused pipeline (tools/prof_tail.py, Llama-3.1-8B shapes): generation 3 is ahead from 5 rows with rotated input; with raw
+    // input its 8 half-waves per workgroup would spend longer on the input Hadamards than generation 2's 16..32, so it starts at 9 rows
+    // and, for wide launches, rotates the activations ONCE first (the role of the reference's A_had temporary, "storage for input transform": quant/exl3_gemm.cu:30, 139-145)
+    const bool g3 = cpw == 0 && gemm3_admits(s, t) && mp >= (s.rotated ? t.gemm3_min_rows : (t.gemm3_min_rows > 9 ? t.gemm3_min_rows : 9));
+    p.pre_xh = g3 && !s.rotated && (long) s.total_cb * mp >= 1024 && (size_t) mp * k * 2 * count <= (size_t) EXL3_WS_XH_BYTES;
+    const bool rot_pass = s.rotated || p.pre_xh;
+    int groups = s.total_cb;                                   // workgroup columns of the grid
+    if (g3)
+    {
+        // generation 3: column blocks per workgroup and the split are chosen together (16-row passes; 32- / 64-row passes keep 4-wave workgroups):
+        // two column blocks per workgroup wherever the instantiation's register budget allows 8 waves (measured best in the whole step; one block
+        // otherwise; four only on request: exl3_set_gemm3_cpw / EXL3_HIP_GEMM3_CPW) -- the split then follows the cost model for that choice
+        p.sel = mp > 32 ? 4 : (mp > 16 ? 2 : 1);
+        const int maxw = g_gemm3_max_waves[s.K - 1](p.sel, rot_pass ? 1 : 0);
+        p.cpw = (t.gemm3_cpw && 4 * t.gemm3_cpw <= maxw) ? t.gemm3_cpw : (maxw >= 8 ? 2 : 1);
+        groups = 0;
+        for (int i = 0; i < count; ++i) groups += (s.ns[i] / 128 + p.cpw - 1) / p.cpw;
+        p.S = gemm3_cost_split(s, mp, num_cus, p.cpw, groups);
+    }
+    else
+    {
+        int fs = s.force_split;
         if (cpw > 0)
         {
-            for (int i = 0; i < count; ++i) total_groups += (ns[i] / 128 + cpw - 1) / cpw;
-            if (force_split == 0)
+            p.cpw = cpw;
+            groups = 0;
+            for (int i = 0; i < count; ++i) groups += (s.ns[i] / 128 + cpw - 1) / cpw;
+            if (fs == 0)
             {
                 // default: about 16 waves per CU in all (4 per SIMD at this layout's 128 VGPRs); tuned values come from the caller
-                const int nbk = k / 128;
-                long want = ((long) ctx->num_cus * 16 + (long) total_groups * cpw - 1) / ((long) total_groups * cpw);
+                long want = ((long) num_cus * 16 + (long) groups * cpw - 1) / ((long) groups * cpw);
                 if (want < 1) want = 1;
-                if (want > nbk) want = nbk;
+                if (want > nb) want = nb;
                 fs = (int) want;
             }
-            else fs = force_split;
         }
-        const int S = g3 ? g3fs : choose_split(gen, total_cb, k, mp, ctx->num_cus, fs);
-        EXL3_CHECK_ARG(S >= 1, "exl3_gemm: internal: split factor %d", S);
-        const int nb = k / 128;
-        const int bps = (nb + S - 1) / S;
-        int cbf = 0; int64_t wso = 0;
-        if (tbl) { args.tbl = *tbl; wso = (int64_t) total_cb * S * mp * 128; }
-        for (int i = 0; i < (tbl ? 0 : count); ++i)
-        {
-            args.mat[i].B = (const uint32_t*) Bs[i];
-            args.mat[i].suh = suhs ? (const half_t*) suhs[i] : nullptr;
-            args.mat[i].svh = svhs ? (const half_t*) svhs[i] : nullptr;
-            args.mat[i].bias = biases ? (const half_t*) biases[i] : nullptr;
-            args.mat[i].C = Cs ? Cs[i] : nullptr;
-            args.mat[i].xh = pre_xh[i] ? (const half_t*) pre_xh[i] : (xhs ? (const half_t*) xhs[i] : nullptr);
-            args.mat[i].xsum = xsums ? xsums[i] : nullptr;
-            args.mat[i].n = ns[i];
-            args.mat[i].cb_first = cbf;
-            args.mat[i].ws_offset = (int) wso;
-            cbf += cpw > 0 ? (ns[i] / 128 + cpw - 1) / cpw : (g3 ? (ns[i] / 128 + g3cpw - 1) / g3cpw : ns[i] / 128);
-            wso += (int64_t) (ns[i] / 128) * S * mp * 128;
-        }
+        else if (s.deferred && fs == 0) fs = deferred_balance_split(s, num_cus, t);
+        p.S = choose_split(s.total_cb, k, num_cus, fs);
+    }
+    const int S = p.S;
+    EXL3_CHECK_ARG(S >= 1, "exl3_gemm: internal: split factor %d", S);
+    const int bps = p.bps = (nb + S - 1) / S;
+    int64_t wso = (int64_t) s.total_cb * S * mp * 128;         // slabs [column block][S][mp][128] of every matrix / slot
+    if (epi)
+    {
+        if (s.epi_mode == GEMV_EPI_NORM) wso += (int64_t) mp * (s.ns[0] / 128);      // + [mp][n/128] sums of squares
+        // one XCD per column block needs (column blocks x S) / 8 consecutive logical workgroups to hold whole column blocks
+        p.xcd_local = (s.epi_mode == GEMV_EPI_RESID && t.tail_xcd_local && s.total_cb % 8 == 0) ? 1 : 0;
+        EXL3_CHECK_ARG(s.total_cb + 1 <= EXL3_NUM_TICKETS, "exl3_gemv: too many column blocks for the ticket table");
+        EXL3_CHECK_ARG(S <= 128, "exl3_gemv: split too deep for the tail epilogue");
+    }
+    EXL3_CHECK_ARG((S == 1 && !s.deferred) || s.atomic_out || wso * 4 <= EXL3_WS_REGION_BYTES, "exl3_gemm: split-k workspace too small");
+    p.ws_floats = (int) wso;
+    p.reduce = S > 1 && !s.deferred;                         // (GEMV_OUT_ATOMIC launches count as deferred: nothing to reduce)
+    const int ng = mp <= 4 ? 1 : (mp <= 8 ? 2 : 4);
+    // generation 4: table launches (MoE) with raw-x / slab-act inputs -- the fp16 gate / up act input and per-matrix widths stay generation 2's;
+    // the mul1 FAST variant needs the producer's block sums with rotated input
+    const bool g4 = !g3 && t.gen4 && ng == 1 && !s.tbl_gen2 && !epi && cpw == 0 && !s.rsd && bps <= 32 && !(rot_pass && var == 1 && s.cb == 2 && !s.xsums);
+    p.gen = g3 ? 3 : (g4 ? 4 : 2);
+    EXL3_CHECK_ARG(!s.fx_zero || g4, "exl3_fx_zero_next: the launch that followed cannot clear the buffer (not a generation-4 launch: rows > 4, a slice of more than 32 Hadamard blocks, a tail / wave-per-column-block mode, or generation 4 switched off)");
+    // 2-D grid (k-slices, column blocks or groups): dispatched x-fastest, i.e. in the order column block * S + slice; the kernels read
+    // their pair from blockIdx instead of dividing a linear id
+    p.grid_x = S; p.grid_y = groups; p.grid_z = 1;
+    if (g3)
+    {
+        // workgroup = 4 cpw waves = cpw adjacent column blocks of one matrix sharing ONE activation tile in LDS (16 rows keep a whole 8-block
+        // slice resident at 4 waves, a whole k = 4096 at 16: one chunk, no second prologue / barrier inside the stream)
+        p.nwv = 4 * p.cpw;
+        p.chunk_blocks = gemm3_chunk_blocks(mp, p.cpw, bps, t.gemm3_chunk_bytes);
+        p.lds = (int) exl3_gemm3_lds_bytes(mp, p.chunk_blocks, p.nwv);
+    }
+    else if (g4)
+    {
+        p.sel = s.qkvm ? 9 : s.attm ? 8 : s.tbl ? (s.in_act ? 7 : 6) : s.in_act ? ((s.flags & GEMV_IN_ACTFX) ? 5 : 3) : (s.in_norm ? (s.in_fx ? 4 : 2) : (rot_pass ? 0 : 1));
+        p.nwv = gemv4_waves(bps, s.deferred, t.max_waves);
+        p.lds = (int) exl3_gemv4_lds_bytes(p.sel, p.nwv, mp, bps);
+    }
+    else
+    {
+        EXL3_CHECK_ARG(!s.atomic_out && !s.in_fx && !s.attm && !s.qkvm && !(s.flags & GEMV_IN_ACTFX) && !(s.tbl && s.in_act), "exl3_gemv_ex: GEMV_OUT_ATOMIC / GEMV_IN_FX / GEMV_IN_ACTFX / GEMV_IN_ATTM / GEMV_IN_QKVM / slab-act table launches are generation-4 launches (m <= 4, slices of <= 32 Hadamard blocks, generation 4 enabled)");
+        p.sel = ng;
+        p.nwv = cpw > 0 ? cpw : gemv2_waves(s, ng, bps, t.max_waves);
+        // activation fragments of one chunk of Hadamard blocks, built once per workgroup: up to ~48 KB, the whole slice when it fits
+        const int AHh = (var == 1 && s.cb != 2) ? 32 : 16;
+        int chunk = (int) ((size_t) 49152 / ((size_t) 8 * mp * AHh * 2));
+        if (chunk < 1) chunk = 1;
+        if (chunk > bps) chunk = bps;
+        EXL3_CHECK_ARG(cpw == 0 || chunk >= bps, "exl3_gemv_ex (cpw): the slice's activation fragments must fit one LDS chunk (use a deeper split)");
+        p.chunk_blocks = chunk;
+        size_t lds = exl3_gemv2_lds_bytes(ng, var, s.cb, p.nwv, mp, chunk);
         if (epi)
         {
-            args.epi = *epi;
-            args.epi.tickets = ctx->tickets;
-            args.epi.ticket_global = total_cb;
-            args.epi.ss_offset = (int) wso;
-            if (epi->mode == GEMV_EPI_NORM) wso += (int64_t) mp * (ns[0] / 128);
-            // one XCD per column block needs (column blocks x S) / 8 consecutive logical workgroups to hold whole column blocks
-            args.epi.xcd_local = (epi->mode == GEMV_EPI_RESID && g_tail_xcd_local && total_cb % 8 == 0) ? 1 : 0;
-            EXL3_CHECK_ARG(total_cb + 1 <= EXL3_NUM_TICKETS, "exl3_gemv: too many column blocks for the ticket table");
-            EXL3_CHECK_ARG(S <= 128, "exl3_gemv: split too deep for the tail epilogue");
+            // tail epilogue: the last workgroup of a column block stages rows_per_pass rows x sets x S slab lines (512 B) in LDS
+            const size_t line_bytes = (size_t) (s.epi_mode == GEMV_EPI_ACT ? 2 : 1) * S * 512;
+            if (lds < line_bytes) lds = line_bytes;
+            int rpp = (int) (lds / line_bytes);
+            if (rpp > mp) rpp = mp;
+            if (rpp > 2 * p.nwv) rpp = 2 * p.nwv;
+            p.rows_per_pass = rpp;
         }
-        EXL3_CHECK_ARG((S == 1 && !deferred) || atomic_out || wso * 4 <= EXL3_WS_REGION_BYTES, "exl3_gemm: split-k workspace too small");
-        float* ws_region = ctx->workspace;
-        if ((S > 1 || deferred) && !atomic_out)
-        {
-            ws_region += ctx->ws_toggle ? EXL3_WS_REGION_BYTES / 4 : 0;
-            ctx->ws_toggle ^= 1;
-            if (slabs_out) for (int i = 0; i < (tbl ? 0 : count); ++i) slabs_out[i] = ws_region + args.mat[i].ws_offset;
-            if (slabs_out && tbl) slabs_out[0] = ws_region;                // indexed form: [slot][column block][S][m][128]
-        }
-        if (S_out) *S_out = S;
-        args.flags = pass_flags;
-        args.A = (const half_t*) A + (size_t) m0 * k;
-        args.workspace = ws_region;
-        {
-            // diagnostics builds (-DG2_TIMING / -DG4_TIMING): phase stamps at 48 MiB of the workspace; EXL3_HIP_TIMING_SLOTS=n (<= 8) rotates n 512-KB slots
-            // over successive launches so that a whole captured step keeps the stamps of its last n GEMV launches (slots 4..7 overlap the
-            // pre-rotation region at 50 MiB: diagnostics only)
-            static const int slots = [] { const char* e = getenv("EXL3_HIP_TIMING_SLOTS"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
-            static unsigned launch_no = 0;
-            args.ws_debug = ctx->workspace + (48ll << 20) / 4 + (size_t) (slots > 1 ? (launch_no++ % (unsigned) slots) : 0) * (512ll << 10) / 4;
-        }
-        args.num_mats = tbl ? 1 : count;
-        args.m = mp;
-        args.k = k;
-        args.S = S;
-        args.kslice = bps * 128;
-        args.c_fp32 = c_fp32;
-        args.c_row_offset = m0;
+        p.lds = (int) lds;
+    }
+    EXL3_CHECK_ARG(groups <= 65535, "exl3_gemm: too many column blocks for one launch");
+    if (g4 && s.tbl)
+    {
+        EXL3_CHECK_ARG(count <= 65535, "exl3_mgemm: too many slots for one launch");
+        p.grid_y = s.ns[0] / 128; p.grid_z = count;          // (k-slices, column blocks of one matrix, slots)
+    }
+    return EXL3_OK;
+}
 
-        args.cpw = cpw;
-        dim3 grid((unsigned) ((cpw > 0 ? total_groups : total_cb) * S));
-        EXL3_CHECK_ARG(!(fxz.ptr && gen == 3), "exl3_fx_zero_next: the launch that followed cannot clear the buffer (not a generation-4 launch: rows > 4, a slice of more than 32 Hadamard blocks, a tail / wave-per-column-block mode, or generation 4 switched off)");
-        if (gen == 3)
+// Pointer and offset bookkeeping of one pass: the kernels' argument block, its workspace region (slab-writing launches alternate between two),
+// the slab addresses handed back, the fx-zero hand-over.  pre_xh[i]: matrix i's activations rotated in front of the launch (p.pre_xh), else null.
+static int gemv_fill_args(const GemvCall& c, const GemvShape& s, const GemvPlan& p, int m0, Exl3DevCtx* ctx, const void* const* pre_xh,
+                          const FxZeroReq& fxz, GemvArgs& args)
+{
+    memset((void*) &args, 0, sizeof(args));
+    const int mp = p.rows, nmat = c.tbl ? 0 : c.count;
+    if (fxz.ptr)
+    {
+        int dev_now = -1;
+        EXL3_CHECK_HIP(hipGetDevice(&dev_now), "exl3_gemv_ex");
+        EXL3_CHECK_ARG(!c.tbl && dev_now == fxz.device, "exl3_fx_zero_next: the launch that follows must be a plain (non-table) generation-4 launch on the device the request was made on");
+        args.fx_zero = fxz.ptr; args.fx_zero_n16 = (int) (fxz.bytes / 16);
+    }
+    args.act_g = c.act_g; args.act_u = c.act_u; args.act_S = c.act_S;
+    args.act_svh_g = (const half_t*) c.act_svh_g; args.act_svh_u = (const half_t*) c.act_svh_u;
+    args.norm_w = (const half_t*) c.norm_w; args.ss_part = c.ss_part; args.eps = c.eps;
+    if (s.in_fx) args.rs_ss_out = c.fx_ss_out;
+    if (c.rsd) { args.rs_slab = c.rsd->slab; args.rs_S = c.rsd->S; args.rs_svh = (const half_t*) c.rsd->svh; args.rs_resid_out = (half_t*) c.rsd->resid_out; args.rs_ss_out = c.rsd->ss_out; }
+    if (c.act_rs) args.act_rs = *c.act_rs;
+    if (c.attm) { args.attm = *c.attm; args.attm.magic_gq = gemv_magic((uint32_t) c.attm->gq); }
+    if (c.qkvm) args.qkvm = *c.qkvm;
+    if (c.tbl) args.tbl = *c.tbl;
+    const int gcb = p.cpw > 0 ? p.cpw : 1;                   // mat[i].cb_first counts the grid's workgroup columns
+    int cbf = 0; int64_t wso = 0;
+    for (int i = 0; i < nmat; ++i)
+    {
+        args.mat[i].B = (const uint32_t*) c.Bs[i];
+        args.mat[i].suh = c.suhs ? (const half_t*) c.suhs[i] : nullptr;
+        args.mat[i].svh = c.svhs ? (const half_t*) c.svhs[i] : nullptr;
+        args.mat[i].bias = c.biases ? (const half_t*) c.biases[i] : nullptr;
+        args.mat[i].C = c.Cs ? c.Cs[i] : nullptr;
+        args.mat[i].xh = pre_xh[i] ? (const half_t*) pre_xh[i] : (c.xhs ? (const half_t*) c.xhs[i] : nullptr);
+        args.mat[i].xsum = c.xsums ? c.xsums[i] : nullptr;
+        args.mat[i].n = c.ns[i];
+        args.mat[i].cb_first = cbf;
+        args.mat[i].ws_offset = (int) wso;
+        cbf += (c.ns[i] / 128 + gcb - 1) / gcb;
+        wso += (int64_t) (c.ns[i] / 128) * p.S * mp * 128;
+    }
+    for (int i = 1; i < GEMV_MAX_MATS; ++i) args.cbf[i - 1] = args.mat[i].cb_first;
+    if (c.epi)
+    {
+        args.epi = *c.epi;
+        args.epi.tickets = ctx->tickets;
+        args.epi.ticket_global = s.total_cb;
+        args.epi.ss_offset = (int) wso;
+        args.epi.xcd_local = p.xcd_local;
+        args.epi.rows_per_pass = p.rows_per_pass;
+    }
+    float* ws_region = ctx->workspace;
+    if ((p.S > 1 || s.deferred) && !s.atomic_out)
+    {
+        ws_region += ctx->ws_toggle ? EXL3_WS_REGION_BYTES / 4 : 0;
+        ctx->ws_toggle ^= 1;
+        if (c.slabs_out) for (int i = 0; i < nmat; ++i) c.slabs_out[i] = ws_region + args.mat[i].ws_offset;
+        if (c.slabs_out && c.tbl) c.slabs_out[0] = ws_region;                // indexed form: [slot][column block][S][m][128]
+    }
+    if (c.S_out) *c.S_out = p.S;
+    args.flags = s.flags | (p.pre_xh ? GEMV_IN_ROTATED : 0);
+    args.A = (const half_t*) c.A + (size_t) m0 * c.k;
+    args.workspace = ws_region;
+    {
+        // diagnostics builds (-DG2_TIMING / -DG4_TIMING): phase stamps at 48 MiB of the workspace; EXL3_HIP_TIMING_SLOTS=n (<= 8) rotates n 512-KB slots
+        // over successive launches so that a whole captured step keeps the stamps of its last n GEMV launches (slots 4..7 overlap the
+        // pre-rotation region at 50 MiB: diagnostics only)
+        static const int slots = [] { const char* e = getenv("EXL3_HIP_TIMING_SLOTS"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
+        static unsigned launch_no = 0;
+        args.ws_debug = ctx->workspace + (48ll << 20) / 4 + (size_t) (slots > 1 ? (launch_no++ % (unsigned) slots) : 0) * (512ll << 10) / 4;
+    }
+    args.num_mats = c.tbl ? 1 : c.count;
+    args.m = mp;
+    args.k = c.k;
+    args.S = p.S;
+    args.kslice = p.bps * 128;
+    args.c_fp32 = c.c_fp32;
+    args.c_row_offset = m0;
+    args.cpw = c.cpw;
+    args.chunk_blocks = p.chunk_blocks;
+    args.magic_m = gemv_magic((uint32_t) mp);
+    if (p.gen != 3) { args.nwv = p.nwv; args.magic_nwv = gemv_magic((uint32_t) p.nwv); args.magic_nhw = gemv_magic((uint32_t) (2 * p.nwv)); }
+    return EXL3_OK;
+}
+
+static int gemv_launch(const GemvShape& s, const GemvPlan& p, int var, GemvArgs& args, hipStream_t st)
+{
+    const dim3 grid((unsigned) p.grid_x, (unsigned) p.grid_y, (unsigned) p.grid_z);
+    if (p.gen == 3) g_launch_gen3[s.K - 1](s.cb, p.sel, var, p.nwv, grid, (size_t) p.lds, st, args);
+    else (p.gen == 4 ? g_launch_gen4 : g_launch_gen2)[s.K - 1](s.cb, var, p.sel, p.nwv, grid, (size_t) p.lds, st, args);
+    int rc = exl3_check_launch("exl3_gemv");
+    if (rc || !p.reduce) return rc;
+    // the reduce kernel walks COLUMN BLOCKS: a launch whose grid counted groups of column blocks (generation 3 with 8- / 16-wave workgroups, the
+    // wave-per-column-block layout) hands it the matrices' first column blocks, not their first groups
+    if (!s.tbl) { int cbc = 0; for (int i = 0; i < s.count; ++i) { args.mat[i].cb_first = cbc; cbc += s.ns[i] / 128; } }
+    const int64_t items = (int64_t) s.total_cb * p.rows;
+    exl3_gemv_reduce_kernel<<<dim3((unsigned) ((items + 7) / 8)), dim3(256), 0, st>>>(args, s.total_cb);
+    return exl3_check_launch("exl3_gemv_reduce");
+}
+
+// The dispatcher: > 0 on success (entry points that promise EXL3_OK map it), < 0 = error code
+static int gemv_run(const GemvCall& c)
+{
+    const FxZeroReq fxz = take_fx_zero();          // one-shot: whatever happens below, the request does not survive this call
+    GemvShape s;
+    int rc = gemv_validate(c, fxz.ptr != nullptr, s);
+    if (rc) return rc;
+    Exl3DevCtx* ctx = exl3_get_ctx(c.stream);
+    if (!ctx) return EXL3_ERR_INIT;
+    const GemvTuning t = gemv_tuning();
+    const int pass_rows = gemv_pass_rows(s, t);
+    for (int m0 = 0; m0 < c.m; m0 += pass_rows)
+    {
+        GemvPlan p; GemvArgs args;
+        if ((rc = gemv_plan_pass(s, (c.m - m0) < pass_rows ? (c.m - m0) : pass_rows, ctx->num_cus, t, p))) return rc;
+        const void* pre_xh[GEMV_MAX_MATS] = { nullptr };
+        const size_t xh_bytes = (size_t) p.rows * c.k * 2;
+        for (int i = 0; p.pre_xh && i < c.count; ++i)
         {
-            const int mt = mp > 32 ? 4 : (mp > 16 ? 2 : 1);
-            // workgroup = 4 g3cpw waves = g3cpw adjacent column blocks of one matrix sharing ONE activation tile in LDS (16 rows keep a whole 8-block
-            // slice resident at 4 waves, a whole k = 4096 at 16: one chunk, no second prologue / barrier inside the stream)
-            const int nwt = 4 * g3cpw;
-            const int chunk = gemm3_chunk_blocks(mp, g3cpw, bps);
-            args.chunk_blocks = chunk;
-            const size_t lds = exl3_gemm3_lds_bytes(mp, chunk, nwt);
-            int total_groups3 = 0;
-            for (int i = 0; i < count; ++i) total_groups3 += (ns[i] / 128 + g3cpw - 1) / g3cpw;
-            EXL3_CHECK_ARG(total_groups3 <= 65535, "exl3_gemm: too many column blocks for one launch");
-            grid = dim3((unsigned) S, (unsigned) total_groups3);              // (k-slices, groups of g3cpw column blocks), as for generation 2 below
-            for (int i = 1; i < GEMV_MAX_MATS; ++i) args.cbf[i - 1] = args.mat[i].cb_first;
-            args.magic_m = gemv_magic((uint32_t) mp);
-            switch (K)
-            {
-                case 1: exl3_gemm3_launch_k1(cb, mt, var, nwt, grid, lds, st, args); break;
-                case 2: exl3_gemm3_launch_k2(cb, mt, var, nwt, grid, lds, st, args); break;
-                case 3: exl3_gemm3_launch_k3(cb, mt, var, nwt, grid, lds, st, args); break;
-                case 4: exl3_gemm3_launch_k4(cb, mt, var, nwt, grid, lds, st, args); break;
-                case 5: exl3_gemm3_launch_k5(cb, mt, var, nwt, grid, lds, st, args); break;
-                case 6: exl3_gemm3_launch_k6(cb, mt, var, nwt, grid, lds, st, args); break;
-                case 7: exl3_gemm3_launch_k7(cb, mt, var, nwt, grid, lds, st, args); break;
-                case 8: exl3_gemm3_launch_k8(cb, mt, var, nwt, grid, lds, st, args); break;
-            }
+            // identical suh -> one rotation serves both (gate / up of some checkpoints share it; cheap pointer test)
+            for (int j = 0; j < i && !pre_xh[i]; ++j) if (c.suhs[j] == c.suhs[i]) pre_xh[i] = pre_xh[j];
+            if (pre_xh[i]) continue;
+            void* dst = (char*) ctx->workspace + EXL3_WS_XH_OFFSET + (size_t) i * xh_bytes;
+            if ((rc = exl3_had_r_128((const half_t*) c.A + (size_t) m0 * c.k, dst, c.suhs[i], nullptr, 1.0f, p.rows, c.k, 0, c.stream)) != EXL3_OK) return rc;
+            pre_xh[i] = dst;
         }
-        else
-        {
-            const int ng = mp <= 4 ? 1 : (mp <= 8 ? 2 : 4);
-            const bool rot_pass = (pass_flags & GEMV_IN_ROTATED) != 0;
-            // table launches (MoE): raw-x / slab-act inputs; the fp16 gate / up act input (tbl->act_u) stays generation 2's
-            bool g4 = gemv_gen4() && ng == 1 && (!tbl || (!tbl->act_u && !tbl->n_list)) && !epi && cpw == 0 && !rsd && bps <= 32;
-            if (g4 && rot_pass && var == 1 && cb == 2)
-                for (int i = 0; i < count; ++i) if (!args.mat[i].xsum) g4 = false;      // the mul1 FAST variant needs the producer's block sums
-            EXL3_CHECK_ARG(g4 || !fxz.ptr, "exl3_fx_zero_next: the launch that followed cannot clear the buffer (not a generation-4 launch: rows > 4, a slice of more than 32 Hadamard blocks, a tail / wave-per-column-block mode, or generation 4 switched off)");
-            if (g4)
-            {
-                const int mode = qkvm ? 9 : attm ? 8 : tbl ? (in_act ? 7 : 6) : in_act ? ((flags & GEMV_IN_ACTFX) ? 5 : 3) : (in_norm ? (in_fx ? 4 : 2) : (rot_pass ? 0 : 1));
-                if (fxz.ptr)
-                {
-                    int dev_now = -1;
-                    EXL3_CHECK_HIP(hipGetDevice(&dev_now), "exl3_gemv_ex");
-                    EXL3_CHECK_ARG(!tbl && dev_now == fxz.device, "exl3_fx_zero_next: the launch that follows must be a plain (non-table) generation-4 launch on the device the request was made on");
-                    args.fx_zero = fxz.ptr; args.fx_zero_n16 = (int) (fxz.bytes / 16); fxz.ptr = nullptr;
-                }
-                const int units4 = bps * 4;
-                int nwv4 = 8;
-                if (nwv4 > (bps > 4 ? bps : 4)) nwv4 = bps > 4 ? bps : 4;
-                if (deferred && nwv4 > 4 && bps <= 16) nwv4 = 4;                       // (generation 2's measured choices, below)
-                if (g_gemv_nwv < 0) nwv4 = -g_gemv_nwv < 8 ? -g_gemv_nwv : 8;
-                if (nwv4 > units4) nwv4 = units4;
-                if (g_gemv_nwv > 0 && nwv4 > g_gemv_nwv) nwv4 = g_gemv_nwv;
-                if (nwv4 < 1) nwv4 = 1;
-                const size_t lds4 = exl3_gemv4_lds_bytes(mode, nwv4, mp, bps);
-                EXL3_CHECK_ARG(grid.x / (unsigned) S <= 65535u, "exl3_gemm: too many column blocks for one launch");
-                grid = dim3((unsigned) S, grid.x / (unsigned) S);
-                if (tbl)
-                {
-                    EXL3_CHECK_ARG(count <= 65535, "exl3_mgemm: too many slots for one launch");
-                    grid = dim3((unsigned) S, (unsigned) (ns[0] / 128), (unsigned) count);       // (k-slices, column blocks of one matrix, slots)
-                }
-                for (int i = 1; i < GEMV_MAX_MATS; ++i) args.cbf[i - 1] = args.mat[i].cb_first;
-                args.nwv = nwv4;
-                args.magic_m = gemv_magic((uint32_t) mp); args.magic_nwv = gemv_magic((uint32_t) nwv4); args.magic_nhw = gemv_magic((uint32_t) (2 * nwv4));
-                switch (K)
-                {
-                    case 1: exl3_gemv4_launch_k1(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                    case 2: exl3_gemv4_launch_k2(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                    case 3: exl3_gemv4_launch_k3(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                    case 4: exl3_gemv4_launch_k4(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                    case 5: exl3_gemv4_launch_k5(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                    case 6: exl3_gemv4_launch_k6(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                    case 7: exl3_gemv4_launch_k7(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                    case 8: exl3_gemv4_launch_k8(cb, var, mode, nwv4, grid, lds4, st, args); break;
-                }
-            }
-            else
-            {
-            EXL3_CHECK_ARG(!atomic_out && !in_fx && !attm && !qkvm && !(flags & GEMV_IN_ACTFX) && !(tbl && in_act), "exl3_gemv_ex: GEMV_OUT_ATOMIC / GEMV_IN_FX / GEMV_IN_ACTFX / GEMV_IN_ATTM / GEMV_IN_QKVM / slab-act table launches are generation-4 launches (m <= 4, slices of <= 32 Hadamard blocks, generation 4 enabled)");
-            int nwv = 16 / ng;                                   // partial-sum LDS: nwv * 4*ng rows * 512 B <= 32 KB
-            const int units = bps * (8 / G2_PF);                 // the waves split the slice's tile rows in units of G2_PF
-            // measured on MI355X (tools/prof_tail.py, batch 1): one wave per Hadamard block of the slice, but at least 4 waves --
-            // more waves than that do not help (the kernel is VALU / fixed-latency bound), fewer starve the short slices
-            if (nwv > (bps > 4 ? bps : 4)) nwv = bps > 4 ? bps : 4;
-            // deferred launches keep every workgroup resident (balanced split above): 4 waves = one per SIMD per workgroup with equal
-            // rows each, so no SIMD ends up with an extra wave (tools/gemv_timeline.py: down_proj's 7-wave workgroups left a
-            // 4/4/3/3 SIMD load and a 1.8 us wait at the workgroup barrier)
-            if (deferred && nwv > 4 && bps <= 16) nwv = 4;
-            // variants above 64 VGPRs (3INST/MCG decode, NORM prep, K >= 5 rings) fit 7 or 6 waves per SIMD: three 8-wave workgroups per
-            // CU instead of one 16-wave workgroup (tools/bench_lmhead.py: lm_head 3INST 105 -> 87 us, NORM 92 -> 81 us)
-            if (!deferred && ng == 1 && (cb != 2 || tbl || K >= 5) && nwv > 8) nwv = 8;
-            if (in_act && nwv > 4) nwv = 4;                      // (classic layout) ACT-mode kernels are built for 4-wave workgroups (256 VGPRs available)
-            if (g_gemv_nwv < 0) nwv = (-g_gemv_nwv < 16 / ng) ? -g_gemv_nwv : 16 / ng;      // tuning: forced wave count
-            if (in_act && nwv > 4) nwv = 4;
-            if (nwv > units) nwv = units;
-            if (g_gemv_nwv > 0 && nwv > g_gemv_nwv) nwv = g_gemv_nwv;
-            if (nwv < 1) nwv = 1;
-            if (cpw > 0) nwv = cpw;                              // one wave per column block of the group
-            // activation fragments of one chunk of Hadamard blocks, built once per workgroup: up to ~48 KB, the whole slice when it fits
-            const int AHh = (var == 1 && cb != 2) ? 32 : 16;
-            int chunk = (int) ((size_t) 49152 / ((size_t) 8 * mp * AHh * 2));
-            if (chunk < 1) chunk = 1;
-            if (chunk > bps) chunk = bps;
-            EXL3_CHECK_ARG(cpw == 0 || chunk >= bps, "exl3_gemv_ex (cpw): the slice's activation fragments must fit one LDS chunk (use a deeper split)");
-            args.chunk_blocks = chunk;
-            size_t lds = exl3_gemv2_lds_bytes(ng, var, cb, nwv, mp, chunk);
-            if (epi)
-            {
-                // tail epilogue: the last workgroup of a column block stages rows_per_pass rows x sets x S slab lines (512 B) in LDS
-                const size_t line_bytes = (size_t) epi_sets * S * 512;
-                if (lds < line_bytes) lds = line_bytes;
-                int rpp = (int) (lds / line_bytes);
-                if (rpp > mp) rpp = mp;
-                if (rpp > 2 * nwv) rpp = 2 * nwv;
-                args.epi.rows_per_pass = rpp;
-            }
-            // 2-D grid (k-slices, column blocks or groups): dispatched x-fastest, i.e. in the order column block * S + slice; the kernel reads
-            // its pair from blockIdx instead of dividing a linear id (exl3_gemv2.kspec.hip prologue)
-            EXL3_CHECK_ARG(grid.x / (unsigned) S <= 65535u, "exl3_gemm: too many column blocks for one launch");
-            grid = dim3((unsigned) S, grid.x / (unsigned) S);
-            for (int i = 1; i < GEMV_MAX_MATS; ++i) args.cbf[i - 1] = args.mat[i].cb_first;
-            args.nwv = nwv;
-            args.magic_m = gemv_magic((uint32_t) mp); args.magic_nwv = gemv_magic((uint32_t) nwv); args.magic_nhw = gemv_magic((uint32_t) (2 * nwv));
-            switch (K)
-            {
-                case 1: exl3_gemv2_launch_k1(cb, var, ng, nwv, grid, lds, st, args); break;
-                case 2: exl3_gemv2_launch_k2(cb, var, ng, nwv, grid, lds, st, args); break;
-                case 3: exl3_gemv2_launch_k3(cb, var, ng, nwv, grid, lds, st, args); break;
-                case 4: exl3_gemv2_launch_k4(cb, var, ng, nwv, grid, lds, st, args); break;
-                case 5: exl3_gemv2_launch_k5(cb, var, ng, nwv, grid, lds, st, args); break;
-                case 6: exl3_gemv2_launch_k6(cb, var, ng, nwv, grid, lds, st, args); break;
-                case 7: exl3_gemv2_launch_k7(cb, var, ng, nwv, grid, lds, st, args); break;
-                case 8: exl3_gemv2_launch_k8(cb, var, ng, nwv, grid, lds, st, args); break;
-            }
-            }
-        }
-        int rc = exl3_check_launch("exl3_gemv");
-        if (rc) return rc;
-        if (S > 1 && !deferred)
-        {
-            // (GEMV_OUT_ATOMIC launches count as deferred: nothing to reduce)
-            // the reduce kernel walks COLUMN BLOCKS: a launch whose grid counted groups of column blocks (generation 3 with 8- / 16-wave workgroups, the
-            // wave-per-column-block layout) hands it the matrices' first column blocks, not their first groups
-            if (!tbl) { int cbc = 0; for (int i = 0; i < count; ++i) { args.mat[i].cb_first = cbc; cbc += ns[i] / 128; } }
-            int64_t items = (int64_t) total_cb * mp;
-            exl3_gemv_reduce_kernel<<<dim3((unsigned) ((items + 7) / 8)), dim3(256), 0, st>>>(args, total_cb);
-            rc = exl3_check_launch("exl3_gemv_reduce");
-            if (rc) return rc;
-        }
+        if ((rc = gemv_fill_args(c, s, p, m0, ctx, pre_xh, fxz, args))) return rc;
+        if ((rc = gemv_launch(s, p, t.variant, args, c.stream))) return rc;
     }
     return 1;
+}
+
+// The per-matrix tables of a one-matrix request (C, svh optional: their tables are left out when null)
+struct GemvOne { const void* B[1]; void* C[1]; const void* suh[1]; const void* svh[1]; const void* bias[1]; int n[1]; };
+static GemvCall gemv_call_one(GemvOne& o, const void* B, void* C, const void* suh, const void* svh, const void* bias, int n, int m, int k, int K, int cb,
+                              void* stream)
+{
+    o.B[0] = B; o.C[0] = C; o.suh[0] = suh; o.svh[0] = svh; o.bias[0] = bias; o.n[0] = n;
+    GemvCall c = {};
+    c.Bs = o.B; c.Cs = C ? o.C : nullptr; c.suhs = o.suh; c.svhs = svh ? o.svh : nullptr; c.biases = o.bias; c.ns = o.n;
+    c.count = 1; c.m = m; c.k = k; c.K = K; c.cb = cb; c.stream = (hipStream_t) stream;
+    return c;
+}
+// A request over `count` matrices given as tables
+static GemvCall gemv_call_many(const void* A, const void* const* Bs, const void* const* suhs, const int* ns, int count, int m, int k, int K, int cb, void* stream)
+{
+    GemvCall c = {};
+    c.A = A; c.Bs = Bs; c.suhs = suhs; c.ns = ns; c.count = count; c.m = m; c.k = k; c.K = K; c.cb = cb; c.stream = (hipStream_t) stream;
+    return c;
 }
 
 extern "C" int exl3_gemm(const void* A, const void* B, void* C, const void* suh, const void* svh, const void* bias,
                          int m, int k, int n, int K, int cb, int c_fp32, int force_split, void* stream)
 {
-    const void* Bs[1] = { B }; void* Cs[1] = { C }; const void* su[1] = { suh }; const void* sv[1] = { svh };
-    const void* bi[1] = { bias }; int ns[1] = { n };
-    return run_mgemm(A, Bs, Cs, su, sv, bi, ns, 1, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream);
+    GemvOne o;
+    GemvCall c = gemv_call_one(o, B, C, suh, svh, bias, n, m, k, K, cb, stream);
+    c.A = A; c.c_fp32 = c_fp32; c.force_split = force_split;
+    return gemv_run(c);
 }
 
 extern "C" int exl3_mgemm(const void* A, const void* const* Bs, void* const* Cs, const void* const* suhs, const void* const* svhs,
                           const int* ns, int count, int m, int k, int K, int cb, int c_fp32, int force_split, void* stream)
 {
     EXL3_CHECK_ARG(Bs && Cs && suhs && svhs && ns, "exl3_mgemm: null table");
-    return run_mgemm(A, Bs, Cs, suhs, svhs, nullptr, ns, count, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream);
+    GemvCall c = gemv_call_many(A, Bs, suhs, ns, count, m, k, K, cb, stream);
+    c.Cs = Cs; c.svhs = svhs; c.c_fp32 = c_fp32; c.force_split = force_split;
+    return gemv_run(c);
 }
 
 // Extended launch used by the fused decode pipeline (exl3_glue.hip): optional pre-rotated inputs per matrix and/or deferred
@@ -727,7 +791,10 @@ extern "C" int exl3_gemv_ex(const void* A, const void* const* xhs, const float* 
 {
     EXL3_CHECK_ARG(Bs && ns, "exl3_gemv_ex: null table");
     EXL3_CHECK_ARG(!(flags & GEMV_IN_NORM), "exl3_gemv_ex: use exl3_gemv_ex_norm for GEMV_IN_NORM");
-    return run_mgemm(A, Bs, Cs, suhs, svhs, biases, ns, count, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream, flags, xhs, xsums, slabs_out, S_out);
+    GemvCall c = gemv_call_many(A, Bs, suhs, ns, count, m, k, K, cb, stream);
+    c.Cs = Cs; c.svhs = svhs; c.biases = biases; c.c_fp32 = c_fp32; c.force_split = force_split; c.flags = flags;
+    c.xhs = xhs; c.xsums = xsums; c.slabs_out = slabs_out; c.S_out = S_out;
+    return gemv_run(c);
 }
 
 // exl3_gemv_ex whose input A is the fp16 residual stream: RMSNorm (norm_w, eps; per-block sums of squares ss_part [m][k/128] from
@@ -737,14 +804,28 @@ extern "C" int exl3_gemv_ex_norm(const void* resid, const void* norm_w, const fl
                                  int m, int k, int K, int cb, int c_fp32, int flags, int force_split, float** slabs_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(Bs && ns && resid, "exl3_gemv_ex_norm: null table");
-    return run_mgemm(resid, Bs, Cs, suhs, svhs, biases, ns, count, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream,
-                     (flags & GEMV_OUT_DEFERRED) | GEMV_IN_NORM, nullptr, nullptr, slabs_out, S_out, nullptr, norm_w, ss_part, eps);
+    GemvCall c = gemv_call_many(resid, Bs, suhs, ns, count, m, k, K, cb, stream);
+    c.Cs = Cs; c.svhs = svhs; c.biases = biases; c.c_fp32 = c_fp32; c.force_split = force_split; c.flags = (flags & GEMV_OUT_DEFERRED) | GEMV_IN_NORM;
+    c.slabs_out = slabs_out; c.S_out = S_out; c.norm_w = norm_w; c.ss_part = ss_part; c.eps = eps;
+    return gemv_run(c);
 }
 
 // ------------------------------------------------------------------------------------------------
 // GEMV launches with an in-kernel tail epilogue (exl3_gemv2_tail.cuh): a whole sublayer boundary of the decode step per launch.
 // Inputs are either pre-rotated (xhs / xsums from the producing tail or glue kernel) or raw (A + suhs: the kernel rotates).
 // ------------------------------------------------------------------------------------------------
+// one matrix, fp32 slabs, the tail epilogue e; input xh (+ xsum) when given, else A
+static int gemv_run_tail_one(const GemvEpi& e, const void* A, const void* xh, const float* xsum, const void* B, const void* suh, const void* svh, const void* bias,
+                             int m, int k, int n, int K, int cb, int force_split, void* stream)
+{
+    GemvOne o;
+    const void* xhs[1] = { xh }; const float* xss[1] = { xsum };
+    GemvCall c = gemv_call_one(o, B, nullptr, suh, svh, bias, n, m, k, K, cb, stream);
+    c.A = A; c.c_fp32 = 1; c.force_split = force_split; c.epi = &e;
+    if (xh) { c.flags = GEMV_IN_ROTATED; c.xhs = xhs; c.xsums = xss; }
+    return gemv_run(c);
+}
+
 extern "C" int exl3_gemv_norm(const void* A, const void* xh, const float* xsum, const void* B, const void* suh, const void* svh, const void* bias,
                               int m, int k, int n, int K, int cb, void* resid, const void* norm_w, float eps,
                               const void* const* t_suhs, void* const* t_xhs, float* const* t_xsums, int t_count, void* xn_out, void* stream)
@@ -760,10 +841,7 @@ extern "C" int exl3_gemv_norm(const void* A, const void* xh, const float* xsum, 
         EXL3_CHECK_ARG(t_suhs && t_xhs && t_suhs[i] && t_xhs[i], "exl3_gemv_norm: null consumer pointer");
         e.t_suh[i] = (const half_t*) t_suhs[i]; e.t_xh[i] = (half_t*) t_xhs[i]; e.t_xsum[i] = t_xsums ? t_xsums[i] : nullptr;
     }
-    const void* Bs[1] = { B }; const void* su[1] = { suh }; const void* sv[1] = { svh }; const void* bi[1] = { bias };
-    const void* xhs[1] = { xh }; const float* xss[1] = { xsum }; int ns[1] = { n };
-    return run_mgemm(A, Bs, nullptr, su, sv, bi, ns, 1, m, k, K, cb, 1, 0, (hipStream_t) stream, xh ? GEMV_IN_ROTATED : 0,
-                     xh ? xhs : nullptr, xh ? xss : nullptr, nullptr, nullptr, &e);
+    return gemv_run_tail_one(e, A, xh, xsum, B, suh, svh, bias, m, k, n, K, cb, 0, stream);
 }
 
 // o_proj / down_proj with glue_resid inside the launch: resid (fp16, in place) += linear(x), ss_out[m][n/128] = per-block sums of squares of the
@@ -777,10 +855,7 @@ extern "C" int exl3_gemv_resid(const void* A, const void* xh, const float* xsum,
     GemvEpi e; memset((void*) &e, 0, sizeof(e));
     e.mode = GEMV_EPI_RESID;
     e.resid = (half_t*) resid; e.ss_out = ss_out;
-    const void* Bs[1] = { B }; const void* su[1] = { suh }; const void* sv[1] = { svh }; const void* bi[1] = { bias };
-    const void* xhs[1] = { xh }; const float* xss[1] = { xsum }; int ns[1] = { n };
-    return run_mgemm(A, Bs, nullptr, su, sv, bi, ns, 1, m, k, K, cb, 1, force_split, (hipStream_t) stream, xh ? GEMV_IN_ROTATED : 0,
-                     xh ? xhs : nullptr, xh ? xss : nullptr, nullptr, nullptr, &e);
+    return gemv_run_tail_one(e, A, xh, xsum, B, suh, svh, bias, m, k, n, K, cb, force_split, stream);
 }
 
 extern "C" int exl3_gemv_act(const void* A, const void* const* xhs, const float* const* xsums, const void* const* Bs, const void* const* suhs,
@@ -793,8 +868,9 @@ extern "C" int exl3_gemv_act(const void* A, const void* const* xhs, const float*
     e.mode = GEMV_EPI_ACT;
     e.t_count = 1; e.t_suh[0] = (const half_t*) suh_d; e.t_xh[0] = (half_t*) xh_d; e.t_xsum[0] = xsum_d; e.a_out = (half_t*) a_out;
     int ns[2] = { inter, inter };
-    return run_mgemm(A, Bs, nullptr, suhs, svhs, nullptr, ns, 2, m, k, K, cb, 0, 0, (hipStream_t) stream, xhs ? GEMV_IN_ROTATED : 0,
-                     xhs, xsums, nullptr, nullptr, &e);
+    GemvCall c = gemv_call_many(A, Bs, suhs, ns, 2, m, k, K, cb, stream);
+    c.svhs = svhs; c.flags = xhs ? GEMV_IN_ROTATED : 0; c.xhs = xhs; c.xsums = xsums; c.epi = &e;
+    return gemv_run(c);
 }
 
 extern "C" int exl3_gemv_qkv(const void* A, const void* const* xhs, const float* const* xsums, const void* const* Bs, const void* const* suhs,
@@ -817,8 +893,9 @@ extern "C" int exl3_gemv_qkv(const void* A, const void* const* xhs, const float*
     e.block_table = block_table; e.blocks_per_seq = blocks_per_seq; e.page_size = page_size > 0 ? page_size : 256;
     e.k_bits = k_bits; e.v_bits = v_bits; e.hq = heads_q; e.hkv = heads_kv; e.rope_mode = rope_mode;
     int ns[3] = { heads_q * 128, heads_kv * 128, heads_kv * 128 };
-    return run_mgemm(A, Bs, nullptr, suhs, svhs, nullptr, ns, 3, m, k, K, cb, 0, 0, (hipStream_t) stream, xhs ? GEMV_IN_ROTATED : 0,
-                     xhs, xsums, nullptr, nullptr, &e);
+    GemvCall c = gemv_call_many(A, Bs, suhs, ns, 3, m, k, K, cb, stream);
+    c.svhs = svhs; c.flags = xhs ? GEMV_IN_ROTATED : 0; c.xhs = xhs; c.xsums = xsums; c.epi = &e;
+    return gemv_run(c);
 }
 
 // Indexed / weighted multi-matrix launch (MoE): exl3_mgemm with pointer tables (quant/exl3_gemm.cuh:58-78, kernel exl3_gemm_kernel.cuh:88-292).
@@ -826,6 +903,26 @@ extern "C" int exl3_gemv_qkv(const void* A, const void* const* xhs, const float*
 //   re-based to min_index, the remaining slots are skipped; A [bszm_in][m][k] (bszm_in == 1: shared), C [bszm][m][n];
 //   weights (fp16 [bszm]): each slot's output is scaled by its weight inside the output Hadamard scale, then every group of
 //   bszm / num_tokens slots is summed into C[t].
+// The table block of the indexed entries: slot outputs [m][n] apart, slot inputs [m][k] apart or one shared input, no expert range unless set after
+static GemvTable gemv_table(const void* tbl_B, const void* tbl_suh, const void* tbl_svh, const int64_t* indices, const void* weights, void* C, int bszm,
+                            int m, int k, int n, bool shared_in)
+{
+    GemvTable t; memset((void*) &t, 0, sizeof(t));
+    t.B = (const uint64_t*) tbl_B; t.suh = (const uint64_t*) tbl_suh; t.svh = (const uint64_t*) tbl_svh;
+    t.indices = indices; t.weights = (const half_t*) weights; t.C = C;
+    t.bszm = bszm; t.min_index = -1; t.max_index = -1; t.n = n; t.cbs_per_mat = n / 128;
+    t.a_slot_stride = shared_in ? 0 : (int64_t) m * k;
+    t.c_slot_stride = (int64_t) m * n;
+    return t;
+}
+// A table request: `bszm` slots of one width n (the per-matrix tables stay empty: the kernels read the device-side tables of t)
+static GemvCall gemv_call_table(const GemvTable& t, const int* n, const void* A, int m, int k, int K, int cb, void* stream)
+{
+    GemvCall c = {};
+    c.A = A; c.tbl = &t; c.ns = n; c.count = t.bszm; c.m = m; c.k = k; c.K = K; c.cb = cb; c.stream = (hipStream_t) stream;
+    return c;
+}
+
 static int mgemm_indexed_impl(const void* A, const void* act_u, int bszm_in, const void* tbl_B, const void* tbl_suh, const void* tbl_svh,
                               const int64_t* indices, const void* weights, int bszm, void* C, int m, int k, int n, int K, int cb, int c_fp32,
                               int min_index, int max_index, int num_tokens, void* stream);
@@ -848,17 +945,13 @@ extern "C" int exl3_mgemm_indexed_nlist(const void* A, int bszm_in, const void* 
     EXL3_CHECK_ARG(A && tbl_B && tbl_suh && tbl_svh && size_n_list && c_ptrs, "exl3_mgemm (per-matrix widths): null pointer");
     EXL3_CHECK_ARG(bszm >= 1 && (bszm_in == 1 || bszm_in == bszm), "exl3_mgemm: A must have 1 or bszm slots");
     EXL3_CHECK_ARG(m >= 1 && m <= 16, "exl3_mgemm (per-matrix widths): 1..16 rows per slot");
-    GemvTable t; memset((void*) &t, 0, sizeof(t));
-    t.B = (const uint64_t*) tbl_B; t.suh = (const uint64_t*) tbl_suh; t.svh = (const uint64_t*) tbl_svh;
-    t.indices = indices; t.C = (void*) c_ptrs;                        // (never written: every slot's output pointer comes from c_list)
-    t.bszm = bszm; t.min_index = -1; t.max_index = -1; t.n = n_max; t.cbs_per_mat = n_max / 128;
-    t.a_slot_stride = bszm_in == 1 ? 0 : (int64_t) m * k;
+    // (C is never written: every slot's output pointer comes from c_list)
+    GemvTable t = gemv_table(tbl_B, tbl_suh, tbl_svh, indices, nullptr, (void*) c_ptrs, bszm, m, k, n_max, bszm_in == 1);
     t.c_slot_stride = 0;
     t.n_list = size_n_list; t.c_list = (const uint64_t*) c_ptrs;
-    const void* Bs[1] = { tbl_B }; int ns[1] = { n_max };
-    const void* su[1] = { tbl_suh }; const void* sv[1] = { tbl_svh }; void* Cs[1] = { (void*) c_ptrs };
-    return run_mgemm(A, Bs, Cs, su, sv, nullptr, ns, bszm, m, k, K, cb, c_fp32, 0, (hipStream_t) stream, 0, nullptr, nullptr, nullptr, nullptr,
-                     nullptr, nullptr, nullptr, 0.0f, &t);
+    GemvCall c = gemv_call_table(t, &n_max, A, m, k, K, cb, stream);
+    c.c_fp32 = c_fp32;
+    return gemv_run(c);
 }
 
 // exl3_mgemm_indexed whose input is fp16(silu(G_j) * U_j) per slot (G, U: [bszm][m][k] fp16, the gate / up outputs of the routed experts): the
@@ -881,17 +974,11 @@ static int mgemm_indexed_impl(const void* A, const void* act_u, int bszm_in, con
     EXL3_CHECK_ARG(num_tokens >= 1 && bszm % num_tokens == 0, "exl3_mgemm: bszm must be divisible by num_tokens");
     EXL3_CHECK_ARG(num_tokens == 1 || min_index < 0, "exl3_mgemm: multi-token reduction (num_tokens > 1) is not compatible with expert-range filtering (min_index >= 0); TP-sharded experts must use num_tokens == 1");
     EXL3_CHECK_ARG(min_index < 0 || indices, "exl3_mgemm: an expert range needs indices");
-    GemvTable t; memset((void*) &t, 0, sizeof(t));
-    t.B = (const uint64_t*) tbl_B; t.suh = (const uint64_t*) tbl_suh; t.svh = (const uint64_t*) tbl_svh;
-    t.indices = indices; t.weights = (const half_t*) weights; t.C = C;
-    t.bszm = bszm; t.min_index = min_index; t.max_index = max_index; t.n = n; t.cbs_per_mat = n / 128;
-    t.a_slot_stride = bszm_in == 1 ? 0 : (int64_t) m * k;
-    t.c_slot_stride = (int64_t) m * n;
-    t.act_u = (const half_t*) act_u;
-    const void* Bs[1] = { tbl_B }; int ns[1] = { n };
-    const void* su[1] = { tbl_suh }; const void* sv[1] = { tbl_svh }; void* Cs[1] = { C };
-    int rc = run_mgemm(A, Bs, Cs, su, sv, nullptr, ns, bszm, m, k, K, cb, c_fp32, 0, (hipStream_t) stream, 0, nullptr, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, 0.0f, &t);
+    GemvTable t = gemv_table(tbl_B, tbl_suh, tbl_svh, indices, weights, C, bszm, m, k, n, bszm_in == 1);
+    t.min_index = min_index; t.max_index = max_index; t.act_u = (const half_t*) act_u;
+    GemvCall c = gemv_call_table(t, &n, A, m, k, K, cb, stream);
+    c.c_fp32 = c_fp32;
+    int rc = gemv_run(c);
     if (rc < 0) return rc;
     if (weights)
     {
@@ -910,17 +997,11 @@ extern "C" int exl3_mgemm_indexed_act_deferred(const void* G, const void* U, con
 {
     EXL3_CHECK_ARG(G && U && tbl_B && tbl_suh && indices && slab_out && S_out, "exl3_mgemm_indexed_act_deferred: null pointer");
     EXL3_CHECK_ARG(bszm >= 1 && m >= 1 && m <= 4, "exl3_mgemm_indexed_act_deferred: 1..4 rows per slot");
-    GemvTable t; memset((void*) &t, 0, sizeof(t));
-    t.B = (const uint64_t*) tbl_B; t.suh = (const uint64_t*) tbl_suh; t.svh = nullptr;
-    t.indices = indices; t.weights = nullptr; t.C = nullptr;
-    t.bszm = bszm; t.min_index = -1; t.max_index = -1; t.n = n; t.cbs_per_mat = n / 128;
-    t.a_slot_stride = (int64_t) m * k;
-    t.c_slot_stride = (int64_t) m * n;
+    GemvTable t = gemv_table(tbl_B, tbl_suh, nullptr, indices, nullptr, nullptr, bszm, m, k, n, false);
     t.act_u = (const half_t*) U;
-    const void* Bs[1] = { tbl_B }; int ns[1] = { n };
-    const void* su[1] = { tbl_suh };
-    int rc = run_mgemm(G, Bs, nullptr, su, nullptr, nullptr, ns, bszm, m, k, K, cb, 0, 0, (hipStream_t) stream, GEMV_OUT_DEFERRED, nullptr, nullptr, slab_out,
-                       S_out, nullptr, nullptr, nullptr, 0.0f, &t);
+    GemvCall c = gemv_call_table(t, &n, G, m, k, K, cb, stream);
+    c.flags = GEMV_OUT_DEFERRED; c.slabs_out = slab_out; c.S_out = S_out;
+    const int rc = gemv_run(c);
     return rc < 0 ? rc : EXL3_OK;
 }
 
@@ -932,14 +1013,10 @@ extern "C" int exl3_mgemm_indexed_deferred(const void* A, int bszm_in, const voi
 {
     EXL3_CHECK_ARG(A && tbl_B && tbl_suh && slab_out && S_out, "exl3_mgemm_indexed_deferred: null pointer");
     EXL3_CHECK_ARG(bszm >= 1 && (bszm_in == 1 || bszm_in == bszm) && m >= 1 && m <= 4, "exl3_mgemm_indexed_deferred: 1..4 rows per slot; A has 1 or bszm slots");
-    GemvTable t; memset((void*) &t, 0, sizeof(t));
-    t.B = (const uint64_t*) tbl_B; t.suh = (const uint64_t*) tbl_suh;
-    t.indices = indices; t.bszm = bszm; t.min_index = -1; t.max_index = -1; t.n = n; t.cbs_per_mat = n / 128;
-    t.a_slot_stride = bszm_in == 1 ? 0 : (int64_t) m * k;
-    t.c_slot_stride = (int64_t) m * n;
-    const void* Bs[1] = { tbl_B }; int ns[1] = { n }; const void* su[1] = { tbl_suh };
-    int rc = run_mgemm(A, Bs, nullptr, su, nullptr, nullptr, ns, bszm, m, k, K, cb, 0, force_split, (hipStream_t) stream, GEMV_OUT_DEFERRED, nullptr, nullptr, slab_out,
-                       S_out, nullptr, nullptr, nullptr, 0.0f, &t);
+    const GemvTable t = gemv_table(tbl_B, tbl_suh, nullptr, indices, nullptr, nullptr, bszm, m, k, n, bszm_in == 1);
+    GemvCall c = gemv_call_table(t, &n, A, m, k, K, cb, stream);
+    c.force_split = force_split; c.flags = GEMV_OUT_DEFERRED; c.slabs_out = slab_out; c.S_out = S_out;
+    const int rc = gemv_run(c);
     return rc < 0 ? rc : EXL3_OK;
 }
 
@@ -954,16 +1031,12 @@ extern "C" int exl3_mgemm_indexed_act_fx(const float* gu_slabs, int act_S, const
     EXL3_CHECK_ARG(gu_slabs && gu_svh_tbl && tbl_B && tbl_suh && tbl_svh && R, "exl3_mgemm_indexed_act_fx: null pointer");
     EXL3_CHECK_ARG(bszm >= 1 && m >= 1 && m <= 4 && act_S >= 1, "exl3_mgemm_indexed_act_fx: 1..4 rows per slot");
     EXL3_CHECK_ARG(num_tokens >= 1 && bszm % num_tokens == 0, "exl3_mgemm_indexed_act_fx: bszm must be divisible by num_tokens");
-    GemvTable t; memset((void*) &t, 0, sizeof(t));
-    t.B = (const uint64_t*) tbl_B; t.suh = (const uint64_t*) tbl_suh; t.svh = (const uint64_t*) tbl_svh;
-    t.indices = indices; t.weights = (const half_t*) weights; t.C = R;
-    t.bszm = bszm; t.min_index = -1; t.max_index = -1; t.n = n; t.cbs_per_mat = n / 128;
-    t.c_slot_stride = (int64_t) m * n;
+    GemvTable t = gemv_table(tbl_B, tbl_suh, tbl_svh, indices, weights, R, bszm, m, k, n, true);
     t.act_svh = (const uint64_t*) gu_svh_tbl; t.act_up_off = up_off; t.slots_per_token = bszm / num_tokens;
-    const size_t sstride = (size_t) (k / 128) * act_S * m * 128;
-    const void* Bs[1] = { tbl_B }; int ns[1] = { n }; const void* su[1] = { tbl_suh }; const void* sv[1] = { tbl_svh };
-    int rc = run_mgemm(nullptr, Bs, nullptr, su, sv, nullptr, ns, bszm, m, k, K, cb, 0, force_split, (hipStream_t) stream, GEMV_OUT_ATOMIC, nullptr, nullptr, nullptr,
-                       nullptr, nullptr, nullptr, nullptr, 0.0f, &t, gu_slabs, gu_slabs + (size_t) bszm * sstride, act_S);
+    GemvCall c = gemv_call_table(t, &n, nullptr, m, k, K, cb, stream);
+    c.force_split = force_split; c.flags = GEMV_OUT_ATOMIC;
+    c.act_g = gu_slabs; c.act_u = gu_slabs + (size_t) bszm * ((size_t) (k / 128) * act_S * m * 128); c.act_S = act_S;
+    const int rc = gemv_run(c);
     return rc < 0 ? rc : EXL3_OK;
 }
 
@@ -981,10 +1054,11 @@ extern "C" int exl3_gemv_ex_resid(const void* resid_in, const void* norm_w, cons
                                   int count, int m, int k, int K, int cb, int cpw, int force_split, float** slabs_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(Bs && ns && resid_in && suhs, "exl3_gemv_ex_resid: null table");
-    GemvResidIn rsd = { prod_slabs, prod_S, prod_svh, resid_out, ss_out };
-    return run_mgemm(resid_in, Bs, nullptr, suhs, nullptr, nullptr, ns, count, m, k, K, cb, 0, force_split, (hipStream_t) stream,
-                     GEMV_OUT_DEFERRED | GEMV_IN_NORM, nullptr, nullptr, slabs_out, S_out, nullptr, norm_w, ss_prev, eps, nullptr,
-                     nullptr, nullptr, 0, nullptr, nullptr, &rsd, nullptr, cpw > 0 ? cpw : 4);
+    const GemvResidIn rsd = { prod_slabs, prod_S, prod_svh, resid_out, ss_out };
+    GemvCall c = gemv_call_many(resid_in, Bs, suhs, ns, count, m, k, K, cb, stream);
+    c.force_split = force_split; c.flags = GEMV_OUT_DEFERRED | GEMV_IN_NORM; c.slabs_out = slabs_out; c.S_out = S_out;
+    c.norm_w = norm_w; c.ss_part = ss_prev; c.eps = eps; c.rsd = &rsd; c.cpw = cpw > 0 ? cpw : 4;
+    return gemv_run(c);
 }
 
 // The "fx" decode pipeline (round 3): the residual stream lives in a 64-bit fixed-point accumulator R [m][hidden] (value * 2^32).  o_proj / down_proj
@@ -998,9 +1072,10 @@ extern "C" int exl3_gemv_ex_fx(const void* R, const void* norm_w, const float* s
                                float** slabs_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(Bs && ns && R && suhs && ss_prev && ss_out && ss_prev != ss_out, "exl3_gemv_ex_fx: null table / ss_out must differ from ss_prev");
-    return run_mgemm(R, Bs, nullptr, suhs, nullptr, nullptr, ns, count, m, k, K, cb, 0, force_split, (hipStream_t) stream,
-                     GEMV_OUT_DEFERRED | GEMV_IN_NORM | GEMV_IN_FX, nullptr, nullptr, slabs_out, S_out, nullptr, norm_w, ss_prev, eps, nullptr,
-                     nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, ss_out);
+    GemvCall c = gemv_call_many(R, Bs, suhs, ns, count, m, k, K, cb, stream);
+    c.force_split = force_split; c.flags = GEMV_OUT_DEFERRED | GEMV_IN_NORM | GEMV_IN_FX; c.slabs_out = slabs_out; c.S_out = S_out;
+    c.norm_w = norm_w; c.ss_part = ss_prev; c.eps = eps; c.fx_ss_out = ss_out;
+    return gemv_run(c);
 }
 
 // exl3_gemv_ex_fx whose outputs are ADDED into fixed-point accumulators accs[i] (int64 [m][n_i], zero on entry: exl3_fx_zero_next) instead of being
@@ -1010,9 +1085,19 @@ extern "C" int exl3_gemv_ex_fx_atomic(const void* R, const void* norm_w, const f
                                       int cb, int force_split, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(Bs && ns && R && suhs && svhs && accs && ss_prev && ss_out && ss_prev != ss_out, "exl3_gemv_ex_fx_atomic: null table");
-    return run_mgemm(R, Bs, accs, suhs, svhs, nullptr, ns, count, m, k, K, cb, 0, force_split, (hipStream_t) stream,
-                     GEMV_OUT_ATOMIC | GEMV_IN_NORM | GEMV_IN_FX, nullptr, nullptr, nullptr, S_out, nullptr, norm_w, ss_prev, eps, nullptr,
-                     nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, ss_out);
+    GemvCall c = gemv_call_many(R, Bs, suhs, ns, count, m, k, K, cb, stream);
+    c.Cs = accs; c.svhs = svhs; c.force_split = force_split; c.flags = GEMV_OUT_ATOMIC | GEMV_IN_NORM | GEMV_IN_FX; c.S_out = S_out;
+    c.norm_w = norm_w; c.ss_part = ss_prev; c.eps = eps; c.fx_ss_out = ss_out;
+    return gemv_run(c);
+}
+
+// The one-matrix launches whose input is finished inside the launch (ACT / ACTFX / ATTM / QKVM): output final (C, svh, bias), deferred slabs or atomic
+static GemvCall gemv_call_one_ex(GemvOne& o, const void* B, void* C, const void* suh, const void* svh, const void* bias, int n, int m, int k, int K, int cb,
+                                 int c_fp32, int flags, int force_split, float** slab_out, int* S_out, void* stream)
+{
+    GemvCall c = gemv_call_one(o, B, C, suh, svh, bias, n, m, k, K, cb, stream);
+    c.c_fp32 = c_fp32; c.flags = flags & (GEMV_OUT_DEFERRED | GEMV_OUT_ATOMIC); c.force_split = force_split; c.slabs_out = slab_out; c.S_out = S_out;
+    return c;
 }
 
 // down_proj of the fx pipeline: input = fp16(silu(g) * u) formed from the fixed-point gate / up accumulators (int64 [m][k]) with the row-scale
@@ -1022,13 +1107,13 @@ extern "C" int exl3_gemv_ex_actfx(const void* g_acc, const void* u_acc, const fl
                                   int flags, int force_split, float** slab_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(g_acc && u_acc && B && suh && m <= 4, "exl3_gemv_ex_actfx: null pointer / m <= 4");
-    const void* Bs[1] = { B }; void* Cs[1] = { C }; const void* su[1] = { suh }; const void* sv[1] = { svh }; const void* bi[1] = { bias };
-    int ns[1] = { n };
-    GemvRescale rs = { ss_prev, ss_new, hidden, eps };
+    GemvOne o;
+    const GemvRescale rs = { ss_prev, ss_new, hidden, eps };
+    GemvCall c = gemv_call_one_ex(o, B, C, suh, svh, bias, n, m, k, K, cb, 0, flags, force_split, slab_out, S_out, stream);
     // the accumulators travel in the act_g / act_u fields; act_S = 1 and dummy svh pointers satisfy the slab-mode argument checks
-    return run_mgemm(nullptr, Bs, C ? Cs : nullptr, su, svh ? sv : nullptr, bi, ns, 1, m, k, K, cb, 0, force_split, (hipStream_t) stream,
-                     (flags & (GEMV_OUT_DEFERRED | GEMV_OUT_ATOMIC)) | GEMV_IN_ACTFX, nullptr, nullptr, slab_out, S_out, nullptr, nullptr, nullptr, 0.0f, nullptr,
-                     (const float*) g_acc, (const float*) u_acc, 1, suh, suh, nullptr, (ss_prev && ss_new) ? &rs : nullptr, 0);
+    c.flags |= GEMV_IN_ACTFX; c.act_g = (const float*) g_acc; c.act_u = (const float*) u_acc; c.act_S = 1; c.act_svh_g = suh; c.act_svh_u = suh;
+    if (ss_prev && ss_new) c.act_rs = &rs;
+    return gemv_run(c);
 }
 
 // exl3_gemv_ex (raw input A + suhs, deferred output, m <= 4) in the wave-per-column-block layout: cpw column blocks of one matrix per workgroup,
@@ -1037,9 +1122,9 @@ extern "C" int exl3_gemv_ex_wpc(const void* A, const void* const* Bs, const void
                                 int cpw, int force_split, float** slabs_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(Bs && ns && A && suhs && cpw >= 1, "exl3_gemv_ex_wpc: null table / cpw");
-    return run_mgemm(A, Bs, nullptr, suhs, nullptr, nullptr, ns, count, m, k, K, cb, 0, force_split, (hipStream_t) stream, GEMV_OUT_DEFERRED,
-                     nullptr, nullptr, slabs_out, S_out, nullptr, nullptr, nullptr, 0.0f, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                     nullptr, nullptr, cpw);
+    GemvCall c = gemv_call_many(A, Bs, suhs, ns, count, m, k, K, cb, stream);
+    c.force_split = force_split; c.flags = GEMV_OUT_DEFERRED; c.slabs_out = slabs_out; c.S_out = S_out; c.cpw = cpw;
+    return gemv_run(c);
 }
 
 // exl3_gemv_ex_act whose gate / up slabs come from an exl3_gemv_ex_resid launch: g and u are multiplied by the exact-over-estimated RMSNorm
@@ -1050,12 +1135,11 @@ extern "C" int exl3_gemv_ex_act_rs(const float* g_slabs, const float* u_slabs, i
                                    int c_fp32, int flags, int cpw, int force_split, float** slab_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(B && suh && ss_prev && ss_new && hidden % 128 == 0, "exl3_gemv_ex_act_rs: null pointer");
-    const void* Bs[1] = { B }; void* Cs[1] = { C }; const void* su[1] = { suh }; const void* sv[1] = { svh }; const void* bi[1] = { bias };
-    int ns[1] = { n };
-    GemvRescale rs = { ss_prev, ss_new, hidden, eps };
-    return run_mgemm(nullptr, Bs, C ? Cs : nullptr, su, svh ? sv : nullptr, bi, ns, 1, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream,
-                     (flags & (GEMV_OUT_DEFERRED | GEMV_OUT_ATOMIC)), nullptr, nullptr, slab_out, S_out, nullptr, nullptr, nullptr, 0.0f, nullptr,
-                     g_slabs, u_slabs, act_S, svh_g, svh_u, nullptr, &rs, cpw);
+    GemvOne o;
+    const GemvRescale rs = { ss_prev, ss_new, hidden, eps };
+    GemvCall c = gemv_call_one_ex(o, B, C, suh, svh, bias, n, m, k, K, cb, c_fp32, flags, force_split, slab_out, S_out, stream);
+    c.act_g = g_slabs; c.act_u = u_slabs; c.act_S = act_S; c.act_svh_g = svh_g; c.act_svh_u = svh_u; c.act_rs = &rs; c.cpw = cpw;
+    return gemv_run(c);
 }
 
 // o_proj whose input is the decode attention's output, finished inside the launch: `part` = the context-split partial records exl3_attn_decode_qcache_split
@@ -1066,12 +1150,11 @@ extern "C" int exl3_gemv_ex_attm(const float* part, int nsplit, int gq, int bloc
                                  int m, int k, int n, int K, int cb, int c_fp32, int flags, int force_split, float** slab_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(part && B && suh, "exl3_gemv_ex_attm: null pointer");
-    const void* Bs[1] = { B }; void* Cs[1] = { C }; const void* su[1] = { suh }; const void* sv[1] = { svh }; const void* bi[1] = { bias };
-    int ns[1] = { n };
-    GemvAttm at = { part, nsplit, gq, blocks, 0u, head_dim };
-    return run_mgemm(nullptr, Bs, C ? Cs : nullptr, su, svh ? sv : nullptr, bi, ns, 1, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream,
-                     (flags & (GEMV_OUT_DEFERRED | GEMV_OUT_ATOMIC)), nullptr, nullptr, slab_out, S_out, nullptr, nullptr, nullptr, 0.0f, nullptr,
-                     nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, &at);
+    GemvOne o;
+    const GemvAttm at = { part, nsplit, gq, blocks, 0u, head_dim };
+    GemvCall c = gemv_call_one_ex(o, B, C, suh, svh, bias, n, m, k, K, cb, c_fp32, flags, force_split, slab_out, S_out, stream);
+    c.attm = &at;
+    return gemv_run(c);
 }
 
 // o_proj fed straight by the q|k|v launch's deferred slabs (the decode step WITHOUT the attention core: o_proj's input is the finished q): the q|k|v epilogue
@@ -1088,8 +1171,6 @@ extern "C" int exl3_gemv_ex_qkvm(const float* sq, const float* sk, const float* 
     EXL3_CHECK_ARG(B && suh, "exl3_gemv_ex_qkvm: null pointer");
     EXL3_CHECK_ARG(!ss_new || (ss_prev && hidden > 0 && hidden % 128 == 0), "exl3_gemv_ex_qkvm: rescale needs ss_prev and hidden");
     EXL3_CHECK_ARG((head_dim == 64 || head_dim == 128) && heads_kv >= 1 && (heads_kv * head_dim) % 128 == 0, "exl3_gemv_ex_qkvm: head_dim 64 | 128, whole 128-value kv blocks");
-    const void* Bs[1] = { B }; void* Cs[1] = { C }; const void* su[1] = { suh }; const void* svp[1] = { svh }; const void* bi[1] = { bias };
-    int ns[1] = { n };
     GemvQkvm q; memset((void*) &q, 0, sizeof(q));
     q.sq = sq; q.sk = sk; q.sv = sv; q.S = S_qkv; q.rope_mode = rope_mode;
     q.svh_q = (const half_t*) svh_q; q.svh_k = (const half_t*) svh_k; q.svh_v = (const half_t*) svh_v;
@@ -1097,9 +1178,10 @@ extern "C" int exl3_gemv_ex_qkvm(const float* sq, const float* sk, const float* 
     q.rs = GemvRescale{ ss_prev, ss_new, hidden, eps };
     q.q_out = (half_t*) q_out; q.k_cache = (uint32_t*) k_cache; q.k_scales = (half_t*) k_scales; q.v_cache = (uint32_t*) v_cache; q.v_scales = (half_t*) v_scales;
     q.hd = head_dim; q.kvb = heads_kv * head_dim / 128;
-    return run_mgemm(nullptr, Bs, C ? Cs : nullptr, su, svh ? svp : nullptr, bi, ns, 1, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream,
-                     (flags & (GEMV_OUT_DEFERRED | GEMV_OUT_ATOMIC)), nullptr, nullptr, slab_out, S_out, nullptr, nullptr, nullptr, 0.0f, nullptr,
-                     nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, &q);
+    GemvOne o;
+    GemvCall c = gemv_call_one_ex(o, B, C, suh, svh, bias, n, m, k, K, cb, c_fp32, flags, force_split, slab_out, S_out, stream);
+    c.qkvm = &q;
+    return gemv_run(c);
 }
 
 extern "C" int exl3_gemv_ex_act(const float* g_slabs, const float* u_slabs, int act_S, const void* svh_g, const void* svh_u,
@@ -1107,9 +1189,72 @@ extern "C" int exl3_gemv_ex_act(const float* g_slabs, const float* u_slabs, int 
                                 int c_fp32, int flags, int force_split, float** slab_out, int* S_out, void* stream)
 {
     EXL3_CHECK_ARG(B && suh, "exl3_gemv_ex_act: null pointer");
-    const void* Bs[1] = { B }; void* Cs[1] = { C }; const void* su[1] = { suh }; const void* sv[1] = { svh }; const void* bi[1] = { bias };
-    int ns[1] = { n };
-    return run_mgemm(nullptr, Bs, C ? Cs : nullptr, su, svh ? sv : nullptr, bi, ns, 1, m, k, K, cb, c_fp32, force_split, (hipStream_t) stream,
-                     (flags & (GEMV_OUT_DEFERRED | GEMV_OUT_ATOMIC)), nullptr, nullptr, slab_out, S_out, nullptr, nullptr, nullptr, 0.0f, nullptr,
-                     g_slabs, u_slabs, act_S, svh_g, svh_u);
+    GemvOne o;
+    GemvCall c = gemv_call_one_ex(o, B, C, suh, svh, bias, n, m, k, K, cb, c_fp32, flags, force_split, slab_out, S_out, stream);
+    c.act_g = g_slabs; c.act_u = u_slabs; c.act_S = act_S; c.act_svh_g = svh_g; c.act_svh_u = svh_u;
+    return gemv_run(c);
+}
+
+// Diagnostics: what the dispatcher launches for a request of this shape on a chip of num_cus CUs, one GemvPlan record per pass -- gemv_validate and
+// gemv_plan_pass, the functions gemv_run calls, on a request whose operands are stand-ins: no device, no context, the fx-zero request untouched
+// (tests/test_gemv_plan.py replays a recording of the dispatcher's decisions through it).  flags: the GEMV_* bits of exl3_gemv_args.h; operands:
+// EXL3_PLAN_* bits (include/exl3_hip.h); attm_hd != 0: a GEMV_IN_ATTM request; tail_xcd_local < 0: the current setting.
+extern "C" int exl3_gemv_plan(int flags, const int* ns, int count, int m, int k, int K, int cb, int force_split, int cpw, int operands, int epi_mode,
+                              int attm_hd, int attm_nsplit, int num_cus, int tail_xcd_local, int32_t* plans_out, int max_passes, int* passes_out)
+{
+    EXL3_CHECK_ARG(ns && plans_out && passes_out && max_passes >= 1 && num_cus >= 1, "exl3_gemv_plan: null pointer / sizes");
+    static char stand_in[32];
+    void* const P = stand_in;
+    void* ptrs[GEMV_MAX_MATS] = { P, P, P, P };
+    const void* const* cptrs = (const void* const*) ptrs;
+    const float* sums[GEMV_MAX_MATS] = { (const float*) P, (const float*) P, (const float*) P, (const float*) P };
+    const bool table = (operands & EXL3_PLAN_TABLE) != 0;
+    GemvCall c = {};
+    c.ns = ns; c.count = count; c.m = m; c.k = k; c.K = K; c.cb = cb; c.force_split = force_split; c.flags = flags; c.cpw = cpw;
+    c.A = P;
+    if (!table) { c.Bs = cptrs; c.Cs = ptrs; c.suhs = cptrs; c.svhs = cptrs; }
+    if (flags & GEMV_IN_ROTATED) c.xhs = cptrs;
+    if (operands & EXL3_PLAN_XSUMS) c.xsums = sums;
+    if (flags & GEMV_IN_NORM) { c.norm_w = P; c.ss_part = (const float*) P; }
+    if ((flags & GEMV_IN_FX) && !(operands & EXL3_PLAN_NO_SS_OUT)) c.fx_ss_out = (float*) P;
+    if (operands & EXL3_PLAN_ACT) { c.act_g = c.act_u = (const float*) P; c.act_S = 1; if (!table) c.act_svh_g = c.act_svh_u = P; }
+    GemvEpi e; memset((void*) &e, 0, sizeof(e));
+    if (epi_mode) { e.mode = epi_mode; c.epi = &e; }
+    GemvTable t; memset((void*) &t, 0, sizeof(t));
+    if (table)
+    {
+        t.B = t.suh = t.svh = (const uint64_t*) P; t.C = P; t.slots_per_token = 1;
+        if (operands & EXL3_PLAN_TABLE_ACT_U) t.act_u = (const half_t*) P;
+        if (operands & EXL3_PLAN_TABLE_N_LIST) t.n_list = (const int32_t*) P;
+        if (operands & EXL3_PLAN_ACT) t.act_svh = (const uint64_t*) P;
+        c.tbl = &t;
+    }
+    const GemvAttm at = { (const float*) P, attm_nsplit, 1, k / 128, 0u, attm_hd };
+    if (attm_hd) c.attm = &at;
+    GemvQkvm q; memset((void*) &q, 0, sizeof(q));
+    if (operands & EXL3_PLAN_QKVM)
+    {
+        q.sq = q.sk = q.sv = q.rope_sin = q.rope_cos = (const float*) P; q.svh_q = q.svh_k = q.svh_v = (const half_t*) P; q.slots = (const int64_t*) P;
+        q.k_cache = q.v_cache = (uint32_t*) P; q.k_scales = q.v_scales = (half_t*) P; q.S = 1; q.rope_mode = 1; q.hd = 128; q.kvb = 1;
+        c.qkvm = &q;
+    }
+    const GemvResidIn rsd = { (const float*) P, 1, P, (operands & EXL3_PLAN_RESID_ALIAS) ? P : (void*) (stand_in + 16), (float*) P };
+    if (operands & EXL3_PLAN_RESID_IN) c.rsd = &rsd;
+
+    GemvShape s;
+    int rc = gemv_validate(c, false, s);
+    if (rc) return rc;
+    GemvTuning tn = gemv_tuning();
+    if (tail_xcd_local >= 0) tn.tail_xcd_local = tail_xcd_local;
+    const int pass_rows = gemv_pass_rows(s, tn);
+    int passes = 0;
+    for (int m0 = 0; m0 < m; m0 += pass_rows, ++passes)
+    {
+        EXL3_CHECK_ARG(passes < max_passes, "exl3_gemv_plan: more than %d passes", max_passes);
+        GemvPlan p;
+        if ((rc = gemv_plan_pass(s, (m - m0) < pass_rows ? (m - m0) : pass_rows, num_cus, tn, p))) return rc;
+        memcpy(plans_out + passes * EXL3_GEMV_PLAN_INTS, &p, sizeof(p));
+    }
+    *passes_out = passes;
+    return EXL3_OK;
 }

@@ -78,6 +78,24 @@ def set_gemv_gen4(on: bool):
     _lib.lib().exl3_set_gemv_gen4(int(bool(on)))
 
 
+GEMV_PLAN_FIELDS = ("rows", "gen", "sel", "pre_xh", "S", "bps", "nwv", "chunk_blocks", "cpw", "grid_x", "grid_y", "grid_z", "lds", "ws_floats",
+                    "rows_per_pass", "xcd_local", "reduce")
+
+
+def gemv_plan(ns, m: int, k: int, K: int, cb: int, num_cus: int, flags: int = 0, force_split: int = 0, cpw: int = 0, operands: int = 0, epi_mode: int = 0,
+              attm_hd: int = 0, attm_nsplit: int = 0, tail_xcd_local: int = -1, count: int | None = None) -> list[dict]:
+    """Diagnostics (exl3_gemv_plan, no device): what the GEMV dispatcher would launch for this request on a chip of num_cus CUs -- one dict of
+    GEMV_PLAN_FIELDS per pass.  A request the dispatcher refuses raises with its message.  count: slots of a table request (ns = [n])."""
+    ns = [int(n) for n in ns]
+    out = (ctypes.c_int32 * (len(GEMV_PLAN_FIELDS) * 16))()
+    passes = ctypes.c_int(0)
+    _check(_lib.lib().exl3_gemv_plan(int(flags), (ctypes.c_int * len(ns))(*ns), len(ns) if count is None else int(count), int(m), int(k), int(K), int(cb),
+                                     int(force_split), int(cpw), int(operands), int(epi_mode), int(attm_hd), int(attm_nsplit), int(num_cus),
+                                     int(tail_xcd_local), out, 16, ctypes.byref(passes)))
+    w = len(GEMV_PLAN_FIELDS)
+    return [dict(zip(GEMV_PLAN_FIELDS, out[i * w:(i + 1) * w])) for i in range(passes.value)]
+
+
 def set_tail_xcd_local(on: bool):
     """Opt in to the XCD-local tail hand-off of exl3_gemv_resid (default off: agent-scope hand-off, placement-independent).  Enabling probes the
     workgroup -> XCD mapping the mode relies on and raises RuntimeError (mode stays off) if the device does not dispatch block i to XCD i % 8."""

@@ -130,6 +130,27 @@ int exl3_set_gemm3_cpw(int column_blocks_per_workgroup);    /* generation 3, <= 
 int exl3_set_attn_wide_waves(int waves_per_workgroup);       /* decode attention, matrix-pipe kernel: 4 / 8 waves per workgroup (one / two dependent token-step chains per SIMD); 0 = by the split length (default; env EXL3_HIP_ATTN_WIDE_NW).  No reference counterpart: A/B runs and tests */
 int exl3_set_gemm3_min_rows(int min_rows);                   /* passes with >= min_rows rows use the LDS-transpose kernel (exl3_gemm3.kspec.hip); default 5 (9 for raw input), 0 = never */
 int exl3_set_gemv_defer_wg_per_cu(int workgroups_per_cu);      /* deferred-epilogue k-split target, 0 = default (2) */
+/* Diagnostics entry, no reference counterpart: the dispatcher's planner alone, host logic (no device needed).  What every exl3_gemm / exl3_mgemm* / exl3_gemv*
+ * entry would launch for a request of this shape on a chip of num_cus CUs, at the current tuning hooks: one record of EXL3_GEMV_PLAN_INTS int32 per pass of
+ * at most 16 / 32 / 64 rows = {rows, kernel generation 2 | 3 | 4, its instantiation (generation 4: input mode 0..9; 2: rows / 4 = 1 | 2 | 4; 3: 16-row tiles 1 | 2 | 4),
+ * activations pre-rotated by a launch in front, k-slices S, Hadamard blocks per slice, waves per workgroup, blocks per LDS chunk, column blocks per workgroup (0: all
+ * waves share one), grid x, y, z, LDS bytes, workspace floats, tail epilogue rows per pass, tail hand-off inside one XCD, a split-k reduce launch follows}.
+ * flags: EXL3_GEMV_* and the input modes the other entries imply (4 RMSNorm input, 64 fixed-point input, 128 fixed-point gate / up input); operands:
+ * EXL3_PLAN_* = which optional operands the request carries; epi_mode: tail epilogue (0 none, 1 exl3_gemv_norm, 2 _act, 3 _qkv, 4 _resid); attm_hd != 0: the
+ * exl3_gemv_ex_attm input with that head_dim and attm_nsplit context splits; tail_xcd_local: 0 / 1, < 0 = the current setting.  ns: `count` widths (a table
+ * request: one width, count = slots).  Returns the error, and leaves the message, of the entry that would have refused the request; *passes_out = records written. */
+#define EXL3_GEMV_PLAN_INTS 17
+#define EXL3_PLAN_XSUMS        1    /* rotated input comes with per-block sums for every matrix */
+#define EXL3_PLAN_TABLE        2    /* exl3_mgemm_indexed* (pointer tables) */
+#define EXL3_PLAN_TABLE_ACT_U  4    /*   ... with the fp16 gate / up input (exl3_mgemm_indexed_act*) */
+#define EXL3_PLAN_TABLE_N_LIST 8    /*   ... with per-matrix widths (exl3_mgemm_indexed_nlist) */
+#define EXL3_PLAN_ACT          16   /* silu(g) * u input from slabs / accumulators (exl3_gemv_ex_act*, exl3_mgemm_indexed_act_fx) */
+#define EXL3_PLAN_QKVM         32   /* exl3_gemv_ex_qkvm input */
+#define EXL3_PLAN_RESID_IN     64   /* exl3_gemv_ex_resid input */
+#define EXL3_PLAN_RESID_ALIAS  128  /*   ... whose resid_out is resid_in (refused) */
+#define EXL3_PLAN_NO_SS_OUT    256  /* fixed-point input without ss_out (refused) */
+int exl3_gemv_plan(int flags, const int* ns, int count, int m, int k, int K, int cb, int force_split, int cpw, int operands, int epi_mode,
+                   int attm_hd, int attm_nsplit, int num_cus, int tail_xcd_local, int32_t* plans_out, int max_passes, int* passes_out);
 
 /* ---- fused decode pipeline (m <= 16): the reference chains these steps as separate graph nodes inside its BC_* runners
  * (libtorch/attention.cpp:246-504 BC_Attention::run_gr, libtorch/mlp.cpp:14-91 BC_GatedMLP::run_bszN_gr); on MI355X each

@@ -256,3 +256,32 @@ def test_merged_step_boundaries_equal_the_two_launch_forms(dev, m, hidden):
     xb = torch.empty_like(xa); ssb = torch.empty_like(ssa); xhb = torch.full_like(xa, float("nan")); xsb = torch.empty_like(ssa)
     ext.fx_finish_rotate(R0, xb, ssb, w, 1e-5, suh, xhb, xsb, m)
     assert torch.equal(xa, xb) and torch.equal(ssa, ssb) and torch.equal(xha, xhb) and torch.equal(xsa, xsb)
+
+
+@pytest.mark.parametrize("k,ns", [(512, [256]), (1024, [512, 256, 256])])
+def test_plan_query_names_the_split_the_dispatcher_launches(dev, k, ns):
+    """exl3_gemv_plan (the device-free query tests/test_gemv_plan.py replays) against the launch path itself: at this device's CU count and the current
+    tuning hooks, the split S that exl3_gemv_ex returns for a deferred launch -- raw and pre-rotated input, 1 / 4 / 5 / 16 rows: generations 4, 2 and 3 --
+    is the query's S; the 16-row launch with finished output still gives the oracle's rows.  (The smallest shapes with more than one Hadamard block per
+    slice choice and more than one matrix; a query that planned with another CU count or other knobs than the launcher would differ here.)"""
+    from exllamav3_amd import ext
+    ext.set_gemv_variant(1)
+    K, cb = 4, 2
+    cus = ext.g_get_num_sms(dev.index or 0)
+    rng = np.random.default_rng(k)
+    mats = [o.synth_linear(k, n, K, seed=20 + i, realistic=True) for i, n in enumerate(ns)]
+    Bs, suhs, svhs = ([_t(t[i], dev) for t in mats] for i in range(3))
+    for m in (1, 4, 5, 16):
+        x = rng.standard_normal((m, k)).astype(np.float16)
+        xd = _t(x, dev)
+        _, S_raw = ext.exl3_gemv_ex(xd, None, None, Bs, None, suhs, None, m, False, True, ext.GEMV_OUT_DEFERRED)
+        assert S_raw == ext.gemv_plan(ns, m, k, K, cb, cus, flags=ext.GEMV_OUT_DEFERRED)[0]["S"], (m, "raw")
+        xhs = [torch.zeros((m, k), dtype=torch.half, device=dev) for _ in ns]
+        xss = [torch.zeros((m, k // 128), dtype=torch.float32, device=dev) for _ in ns]
+        _, S_rot = ext.exl3_gemv_ex(None, xhs, xss, Bs, None, None, None, m, False, True, ext.GEMV_IN_ROTATED | ext.GEMV_OUT_DEFERRED)
+        assert S_rot == ext.gemv_plan(ns, m, k, K, cb, cus, flags=ext.GEMV_IN_ROTATED | ext.GEMV_OUT_DEFERRED, operands=1)[0]["S"], (m, "rotated")
+    ys = [torch.full((16, n), float("nan"), dtype=torch.half, device=dev) for n in ns]
+    _, S = ext.exl3_gemv_ex(xd, None, None, Bs, ys, suhs, svhs, 16, False, True, 0)
+    assert S == ext.gemv_plan(ns, 16, k, K, cb, cus)[0]["S"]
+    for y, t in zip(ys, mats):
+        assert _rel(y.float().cpu().numpy(), o.linear_forward(x, *t, K, cb).astype(np.float32)) < TOL
