@@ -234,6 +234,10 @@ def _declare(l):
     sig("exl3_embed_rows", vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp)
     # logit processors (exl3_logit_process.hip)
     sig("exl3_logit_process", vp, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, vp, i32, f32, i32, i32, f32, f32, i32, i32, vp, vp, i32, i32, vp)
+    # speculative decoding (exl3_spec.hip)
+    sig("exl3_spec_accept", vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp)
+    sig("exl3_spec_draft_ngram", vp, i32, vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp)
+    sig("exl3_spec_round", vp, vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp, vp, vp)
     sig("exl3_set_gemv_variant", i32)
     sig("exl3_set_gemv_max_waves", i32)
     sig("exl3_set_gemv_gen4", i32)

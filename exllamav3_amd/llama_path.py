@@ -322,17 +322,21 @@ class SyntheticEXL3Llama:
     def alloc_state(self, bsz: int, pos: int = 1000):
         self._alloc_state(bsz, pos, None)
 
-    def _alloc_state(self, bsz: int, pos: int, x):
-        """alloc_state's buffers; x = the input rows (None: alloc_state's random rows, drawn where it always drew them)."""
+    def _alloc_state(self, bsz: int, pos: int, x, one_sequence: bool = False):
+        """alloc_state's buffers; x = the input rows (None: alloc_state's random rows, drawn where it always drew them).  one_sequence (alloc_spec_state): the
+        bsz rows are positions of ONE sequence -- cache pages for one sequence and a block table whose rows all name them."""
         dev, s = self.device, self.shape
         hd = s.head_dim
         kv_dim = self.hkv * hd
         G = kv_dim // 32
         pages_per_seq = self.max_ctx // self.page
-        self.block_table = torch.arange(bsz * pages_per_seq, dtype=torch.int32, device=dev).view(bsz, pages_per_seq)
+        seqs = 1 if one_sequence else bsz
+        self.block_table = torch.arange(seqs * pages_per_seq, dtype=torch.int32, device=dev).view(seqs, pages_per_seq)
+        if one_sequence:
+            self.block_table = self.block_table.repeat(bsz, 1)
         self.cache_seqlens = torch.full((bsz,), pos, dtype=torch.int32, device=dev)
         self.positions = torch.full((bsz,), pos, dtype=torch.int32, device=dev)
-        n_pages = bsz * pages_per_seq
+        n_pages = seqs * pages_per_seq
         self.kcache = [(torch.zeros((n_pages, self.page, G * self.kv_bits), dtype=torch.int32, device=dev),
                         torch.zeros((n_pages, self.page, G), dtype=torch.half, device=dev)) for _ in range(self.n_layers)]
         self.vcache = [(torch.zeros((n_pages, self.page, G * self.kv_bits), dtype=torch.int32, device=dev),
@@ -1047,7 +1051,9 @@ class SyntheticEXL3Llama:
     #: weights are reconstructed once per chunk).  EXL3_HIP_GEN_PREFILL_CHUNK overrides it for A/B runs.
     gen_prefill_chunk = int(os.environ.get("EXL3_HIP_GEN_PREFILL_CHUNK", "4096"))
 
-    def ingest_prompt(self, n_tokens: int, chunk: int | None = None, return_rows: bool = False):
+    def ingest_prompt(self, n_tokens: int, chunk: int | None = None, return_rows: bool = False, *, ids: torch.Tensor | None = None,
+                      block_table: torch.Tensor | None = None, cache_seqlens: torch.Tensor | None = None, attn_lens: torch.Tensor | None = None,
+                      invalid: torch.Tensor | None = None):
         """Prompt tokens 0 .. n_tokens - 1 of every row of the generation state (alloc_gen_state: gs.forced) through the PREFILL route into the generation's own
         cache (self.kcache / self.vcache per layer, through the state's block_table), at most `chunk` tokens per row at a time (default gen_prefill_chunk).  A chunk
         at offset p0 with T tokens: rows from exl3_embed_rows, then per layer RMSNorm -> q|k|v -> RoPE at p0 .. p0 + T - 1 -> quantised append behind
@@ -1055,38 +1061,52 @@ class SyntheticEXL3Llama:
         p0 + T -> o_proj (+ residual) -> norm -> gate|up -> down (+ residual).  Any T >= 1 works (LinearEXL3 routes by row count).  In the last chunk the last layer
         stops behind its cache append: nothing downstream of it is consumed (no final norm, no lm_head).  return_rows (tests): every layer runs to its end and the
         residual stream behind the last layer comes back as fp16 [bsz, n_tokens, hidden].
-        Leaves positions = cache_seqlens = n_tokens and attn_lens = n_tokens + 1 (what a decode step of token n_tokens expects).  Returns the chunk count (or the rows)."""
+        Leaves positions = cache_seqlens = n_tokens and attn_lens = n_tokens + 1 (what a decode step of token n_tokens expects).  Returns the chunk count (or the rows).
+        ids / block_table / cache_seqlens / attn_lens / invalid (all five together; the speculative path: one sequence inside a state of m aliased rows): the int32
+        id matrix [rows, >= n_tokens], the block-table rows and the per-row counters to work on instead of the generation state's; the two counters are left at
+        n_tokens / n_tokens + 1 and self.positions is not touched."""
         from . import sampling
         if self.tp > 1:
             raise NotImplementedError("ingest_prompt: tensor-parallel generation is not built")
         s, hd, dev = self.shape, self.shape.head_dim, self.device
         if hd not in (64, 128):
             raise NotImplementedError("ingest_prompt: the prefill attention takes head_dim 64 or 128")
-        gs, bsz = self.gen, self._state_bsz
+        own = ids is None
+        if own:
+            if not (block_table is None and cache_seqlens is None and attn_lens is None and invalid is None):
+                raise ValueError("ingest_prompt: ids, block_table, cache_seqlens, attn_lens and invalid go together")
+            gs, bsz = self.gen, self._state_bsz
+            ids, block_table, cache_seqlens, attn_lens, invalid = gs.forced, self.block_table, self.cache_seqlens, self.attn_lens, gs.invalid
+        else:
+            if block_table is None or cache_seqlens is None or attn_lens is None or invalid is None:
+                raise ValueError("ingest_prompt: ids, block_table, cache_seqlens, attn_lens and invalid go together")
+            bsz = ids.shape[0]
+            if not (block_table.shape[0] == bsz and cache_seqlens.numel() == bsz and attn_lens.numel() == bsz and invalid.numel() >= bsz):
+                raise ValueError("ingest_prompt: one block-table row and one counter per row of ids")
         n = int(n_tokens)
         chunk = int(self.gen_prefill_chunk if chunk is None else chunk)
         if chunk < 1:
             raise ValueError("ingest_prompt: chunk must be at least 1")
-        if not (0 <= n <= gs.forced.shape[1] and n <= self.max_ctx):
+        if not (0 <= n <= ids.shape[1] and n <= self.max_ctx):
             raise ValueError("ingest_prompt: n_tokens outside the prompt")
         kv_dim = self.hkv * hd
-        n_pages = self.block_table.numel()
+        n_pages = self.kcache[0][0].shape[0]
         if getattr(self, "_ing_pages", None) is None or self._ing_pages[0].shape != (n_pages, self.page, kv_dim):
             self._ing_pages = [torch.zeros((n_pages, self.page, kv_dim), dtype=torch.half, device=dev) for _ in range(2)]
         kd, vd = self._ing_pages
         out, chunks = [], 0
         for p0 in range(0, n, chunk):
             T = min(chunk, n - p0)
-            self.cache_seqlens.fill_(p0)
-            self.attn_lens.fill_(p0 + T)
-            x = sampling.embed_rows(gs.forced, p0, T, gs.embed, gs.invalid, vocab=s.vocab)
+            cache_seqlens.fill_(p0)
+            attn_lens.fill_(p0 + T)
+            x = sampling.embed_rows(ids, p0, T, self.embed_table(), invalid, vocab=s.vocab)
             xn = torch.empty_like(x)
             ao = torch.empty((bsz * T, self.hq * hd), dtype=torch.half, device=dev)
             for li, L in enumerate(self.layers):
                 ext.rms_norm(x, L["norm1"], xn, self.eps)
                 last = p0 + T == n and li == self.n_layers - 1 and not return_rows
-                q = self._prefill_qkv_attend(L, xn, bsz, T, p0, self.kcache[li], self.vcache[li], self.cache_seqlens, self.block_table,
-                                             None if last else (kd, vd, self.attn_lens, ao))
+                q = self._prefill_qkv_attend(L, xn, bsz, T, p0, self.kcache[li], self.vcache[li], cache_seqlens, block_table,
+                                             None if last else (kd, vd, attn_lens, ao))
                 if last:
                     break
                 L["o"].forward_add_residual(q, x)
@@ -1096,7 +1116,9 @@ class SyntheticEXL3Llama:
             chunks += 1
             if return_rows:
                 out.append(x.view(bsz, T, s.hidden))
-        self.positions.fill_(n); self.cache_seqlens.fill_(n); self.attn_lens.fill_(n + 1)
+        if own:
+            self.positions.fill_(n)
+        cache_seqlens.fill_(n); attn_lens.fill_(n + 1)
         return torch.cat(out, dim=1) if return_rows else chunks
 
     def _gen_prime_prefilled(self, chunk: int | None = None) -> int:
@@ -1116,7 +1138,7 @@ class SyntheticEXL3Llama:
         return chunks
 
     def generate(self, prompt_ids, max_new_tokens: int, settings=None, eos_token_id: int | None = None, processors=None, stop_token_ids=None,
-                 stop_check_every: int | None = None, prompt_mode: str = "decode", prefill_chunk: int | None = None) -> torch.Tensor:
+                 stop_check_every: int | None = None, prompt_mode: str = "decode", prefill_chunk: int | None = None, speculative=None) -> torch.Tensor:
         """Generates max_new_tokens tokens behind prompt_ids ([P] or [bsz, P]) from an empty cache, with the decode attention on.  The loop body (decode_step_auto +
         sampler + token feed) is captured ONCE as a graph and replayed P - 1 + max_new_tokens times without a synchronisation or a host read in between (the
         prompt goes through the same step token by token as forced tokens: prompt_mode "decode", the default); one read at the end.
@@ -1130,7 +1152,10 @@ class SyntheticEXL3Llama:
         stop_token_ids (<= 64 ids): the feed marks a row done at its first SAMPLED stop token (a stop id inside the prompt does not count); after every
         stop_check_every replays (default 16) the host reads the 4-byte live word and leaves the loop when no row is live.  The result follows the EOS rules: one
         sequence is cut behind its first stop token (kept), a batch is filled with the first stop id behind it.  gen_stats counts the reads of the live word in
-        host_reads and gains stopped_after (the replay count at which the loop was left early, else None) on this path only."""
+        host_reads and gains stopped_after (the replay count at which the loop was left early, else None) on this path only.
+        speculative: sampling.SpeculativeSettings -- one sequence, several tokens per weight pass where the drafts hold (_generate_speculative); the tokens are
+        those of the same loop without drafts; the prompt always takes the prefill route (prompt_mode is not read), stop_check_every applies with or without
+        stop ids (the loop leaves when the budget is used up), processors and batches are refused.  None (the default): everything above, unchanged."""
         from . import sampling
         if prompt_mode not in ("decode", "prefill"):
             raise ValueError('generate: prompt_mode is "decode" or "prefill"')
@@ -1138,6 +1163,8 @@ class SyntheticEXL3Llama:
             raise NotImplementedError("generate: tensor-parallel sampling (the vocabulary gather) is not built")
         if self.shape.head_dim not in (64, 128):
             raise NotImplementedError("generate: the decode attention takes head_dim 64 or 128")
+        if speculative is not None:
+            return self._generate_speculative(prompt_ids, max_new_tokens, settings, eos_token_id, processors, stop_token_ids, stop_check_every, prefill_chunk, speculative)
         prompt = torch.as_tensor(prompt_ids, dtype=torch.long)
         one = prompt.dim() == 1
         if one:
@@ -1225,6 +1252,174 @@ class SyntheticEXL3Llama:
                     else:
                         new[r, int(hit[0]) + 1:] = eos_token_id
         return new[0] if one else new
+
+    # ---- speculative decoding: one sequence as m aliased rows, accept / draft / feed on the device (csrc/exl3_spec.hip) ------------------------------------
+    #: the launches behind the sampler of a verify step: True = exl3_spec_round (accept + draft + feed in one launch), False = exl3_spec_accept then
+    #: exl3_spec_draft_ngram (tools/bench_generate.py, section speculative, measures both)
+    spec_fold = os.environ.get("EXL3_HIP_SPEC_FOLD", "1") != "0"
+
+    def alloc_spec_state(self, k: int, max_new: int, prompt, settings=None):
+        """The state of a speculative generation of ONE sequence with k drafts per verify step: _alloc_state's buffers for m = k + 1 rows, but cache pages for one
+        sequence and a block table whose m rows all name them (row i of a verify step is position base + i of that sequence); every workspace sized by
+        max_ctx as in alloc_gen_state.  prompt: token ids [P], P >= 1.  Requires P + max_new + k <= max_ctx: the padding rows of the last round append their
+        K / V beyond the token budget.  settings: sampling.SpeculativeSettings (match lengths, script).  Primed: hist[:P] = prompt, base = P - 1, the first
+        round's inputs written by the drafter (the cache is still empty: ingest the prompt's first P - 1 tokens before the first spec_step)."""
+        from types import SimpleNamespace
+        from . import sampling
+        dev = self.device
+        settings = settings or sampling.SpeculativeSettings()                  # (only the match lengths and the script are read here: k = 0 is a legal state)
+        k = int(k)
+        m = k + 1
+        if not (1 <= m <= sampling.MAX_ROWS):
+            raise ValueError("alloc_spec_state: k must be in [0, 15]")
+        prompt = torch.as_tensor(prompt, dtype=torch.long).flatten()
+        P = prompt.numel()
+        if P < 1 or max_new < 0:
+            raise ValueError("alloc_spec_state: the prompt holds at least one token, max_new is not negative")
+        if P + max_new + k > self.max_ctx:
+            raise ValueError(f"alloc_spec_state: prompt ({P}) + new tokens ({max_new}) + drafts ({k}) exceed max_ctx ({self.max_ctx})")
+        if int(prompt.min()) < 0 or int(prompt.max()) >= self.shape.vocab:
+            raise ValueError("alloc_spec_state: prompt token outside the vocabulary")
+        embed = self.embed_table()
+        self._alloc_state(m, self.max_ctx - 1, torch.zeros((m, self.shape.hidden), dtype=torch.half, device=dev), one_sequence=True)
+        script = None
+        if settings.script is not None:
+            sc = torch.as_tensor(settings.script, dtype=torch.long).flatten()[:self.max_ctx]
+            script = torch.full((self.max_ctx,), -1, dtype=torch.int32)
+            script[:sc.numel()] = sc.to(torch.int32)
+            script = script.to(dev)
+        i32 = torch.int32
+        self.spec = SimpleNamespace(
+            k=k, m=m, P=P, max_new=int(max_new), embed=embed, prompt=prompt.to(i32).to(dev), script=script, stop_ids=None,
+            match_min=int(settings.ngram_match_min), match_max=int(settings.ngram_match_max),
+            hist=torch.empty((self.max_ctx,), dtype=i32, device=dev), state=torch.empty((sampling.SPEC_STATE_WORDS,), dtype=i32, device=dev),
+            state0=torch.tensor([P - 1, 0, 1 if max_new > 0 else 0, 0, 0, 0, 0, 0, 0], dtype=i32, device=dev),
+            round=torch.empty((1,), dtype=torch.int64, device=dev), in_tokens=torch.empty((m,), dtype=i32, device=dev),
+            sampled=torch.empty((m,), dtype=i32, device=dev), tokens_out=torch.empty((max(int(max_new), 1),), dtype=i32, device=dev),
+            ing_invalid=torch.zeros((1,), dtype=i32, device=dev), ws=sampling.workspace(m, dev))
+        self.spec.live = self.spec.state[sampling.SPEC_LIVE:sampling.SPEC_LIVE + 1]            # the 4-byte word the host polls
+        self._spec_prime()
+        return self.spec
+
+    def _spec_prime(self):
+        """(Re)starts the speculative state: history = the prompt, base = P - 1, nothing produced, round word 0, then the drafter's launch writes the inputs of
+        the first verify step.  The cache is left as it is (positions below P - 1 hold the ingested prompt; everything from P - 1 on is rewritten)."""
+        from . import sampling
+        sp = self.spec
+        sp.hist.fill_(-1); sp.hist[:sp.P] = sp.prompt
+        sp.state.copy_(sp.state0); sp.round.zero_(); sp.tokens_out.fill_(-1); sp.sampled.fill_(-1)
+        sampling.spec_draft(sp.hist, sp.state, sp.in_tokens, sp.embed, self.x0, self.positions, self.cache_seqlens, self.attn_lens, sp.k, sp.max_new,
+                            sp.match_min, sp.match_max, script=sp.script, vocab=self.shape.vocab)
+
+    def spec_step(self, ka, stop: bool = False):
+        """The loop body of speculative generation -- kernel launches only (graph-capturable): the verify step over the m aliased rows, the sampler over the m
+        logits rows with step word = round, then accept / draft / feed (one launch, or two with spec_fold off).
+        The verify step is decode_step_fused for EVERY m, m = 2 included, not decode_step_auto: row i attends over what rows < i append in the same step, so
+        all m appends must be complete before any row attends.  decode_step_fused appends every row in glue_qkv and attends in a later launch.
+        decode_step_fx (what decode_step_auto picks at 2-4 rows) appends inside the context-split attention launch itself, where the workgroup that holds a
+        row's new token writes it while other rows' workgroups already read; the persistent step takes one row only."""
+        from . import sampling
+        sp = self.spec
+        logits = self.decode_step_fused()
+        sampling.sample(logits, ka, sp.round, size=self.shape.vocab, out=sp.sampled, ws=sp.ws)
+        stop_ids = sp.stop_ids if stop else None
+        if self.spec_fold:
+            sampling.spec_round(sp.sampled, sp.in_tokens, sp.state, sp.round, sp.hist, sp.tokens_out, sp.embed, self.x0, self.positions, self.cache_seqlens,
+                                self.attn_lens, sp.k, sp.match_min, sp.match_max, script=sp.script, stop_ids=stop_ids, vocab=self.shape.vocab, max_new=sp.max_new)
+        else:
+            sampling.spec_accept(sp.sampled, sp.in_tokens, sp.state, sp.round, sp.hist, sp.tokens_out, self.shape.vocab, stop_ids=stop_ids, max_new=sp.max_new)
+            sampling.spec_draft(sp.hist, sp.state, sp.in_tokens, sp.embed, self.x0, self.positions, self.cache_seqlens, self.attn_lens, sp.k, sp.max_new,
+                                sp.match_min, sp.match_max, script=sp.script, vocab=self.shape.vocab)
+
+    def _spec_ingest(self, chunk: int | None = None) -> int:
+        """Prompt tokens 0 .. P - 2 of the speculative state through the prefill route into the one sequence's cache (ingest_prompt over row 0's block-table row
+        and counters; the prime behind it rewrites the counters).  Returns the chunk count."""
+        sp = self.spec
+        return self.ingest_prompt(sp.P - 1, chunk, ids=sp.hist.view(1, -1), block_table=self.block_table[:1], cache_seqlens=self.cache_seqlens[:1],
+                                  attn_lens=self.attn_lens[:1], invalid=sp.ing_invalid)
+
+    def _generate_speculative(self, prompt_ids, max_new_tokens, settings, eos_token_id, processors, stop_token_ids, stop_check_every, prefill_chunk, spec):
+        """generate(..., speculative=spec): one sequence; every verify step (spec_step) runs num_draft_tokens + 1 rows and commits the drafts that equal the
+        target's own tokens plus one.  Prompt tokens 0 .. P - 2 go through the prefill route (P == 1: nothing to ingest), one uncaptured round runs, the state
+        is reset, the body is captured ONCE and replayed at most max_new_tokens times; after every stop_check_every replays (default 16) the host reads the
+        4-byte live word and leaves when it is 0 (budget used up, stop token, invalid); one read at the end.  gen_stats gains spec_rounds, spec_drafted and
+        spec_accepted (live rounds, drafts fed, drafts accepted: spec_accepted + spec_rounds = tokens produced).
+        Sampled modes: the draft is deterministic and row i's token is drawn from the target's distribution with noise that depends on (row, round) only; a
+        draft is accepted iff it equals that token, else the token itself is emitted -- the output distribution is exactly the target's."""
+        from . import sampling
+        if not isinstance(spec, sampling.SpeculativeSettings):
+            raise TypeError("generate: speculative must be a sampling.SpeculativeSettings")
+        if processors is not None:
+            raise NotImplementedError("generate: logit processors under speculation are not built (the penalty windows of rows >= 1 would have to include the drafts)")
+        prompt = torch.as_tensor(prompt_ids, dtype=torch.long)
+        one = prompt.dim() == 1
+        if not one:
+            if not (prompt.dim() == 2 and prompt.shape[0] == 1):
+                raise NotImplementedError("generate: speculative decoding of a batch of sequences is not built")
+            prompt = prompt[0]
+        P, max_new, k = prompt.numel(), int(max_new_tokens), int(spec.num_draft_tokens)
+        if P < 1:
+            raise ValueError("generate: the prompt holds at least one token")
+        if P + max_new + k > self.max_ctx:
+            raise ValueError(f"generate: prompt ({P}) + new tokens ({max_new}) + draft tokens ({k}) exceed max_ctx ({self.max_ctx})")
+        ka = (settings or sampling.SamplerSettings(temperature=0.0)).kernel_args()
+        stop = None
+        if stop_token_ids is not None:
+            stop = [int(t) for t in stop_token_ids]
+            if not (1 <= len(stop) <= sampling.MAX_STOP_IDS):
+                raise ValueError("generate: 1 to 64 stop token ids")
+        every = 16 if stop_check_every is None else int(stop_check_every)
+        if every < 1:
+            raise ValueError("generate: stop_check_every must be at least 1")
+        att_before = self.with_attention
+        self.with_attention = True
+        try:
+            sp = self.alloc_spec_state(k, max_new, prompt, spec)
+            self.gen_stats = {"graph_captures": 0, "graph_replays": 0, "host_reads": 0}
+            if stop is not None:
+                self.gen_stats["stopped_after"] = None
+                sp.stop_ids = torch.tensor(stop, dtype=torch.int32, device=self.device)
+            if max_new > 0:
+                if P > 1:
+                    self.gen_stats["prefill_chunks"] = self._spec_ingest(prefill_chunk)
+                    self.gen_stats["prefill_tokens"] = P - 1
+                    self._spec_prime()
+                self.spec_step(ka, stop is not None)               # uncaptured: plan creation
+                self._spec_prime()
+                st = torch.cuda.Stream(device=self.device)
+                st.wait_stream(torch.cuda.current_stream(self.device))
+                with torch.cuda.stream(st):
+                    graph = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(graph, stream=st):
+                        self.spec_step(ka, stop is not None)
+                torch.cuda.current_stream(self.device).wait_stream(st)
+                self.gen_stats["graph_captures"] = 1
+                for i in range(max_new):
+                    graph.replay()
+                    self.gen_stats["graph_replays"] += 1
+                    if (i + 1) % every == 0 and i + 1 < max_new:
+                        self.gen_stats["host_reads"] += 1
+                        if int(sp.live.cpu()) == 0:                # the 4-byte live word (synchronises)
+                            if stop is not None:
+                                self.gen_stats["stopped_after"] = i + 1
+                            break
+            host = torch.cat([sp.tokens_out, sp.state, sp.ing_invalid]).cpu()                  # the one read (synchronises)
+            self.gen_stats["host_reads"] += 1
+        finally:
+            self.with_attention = att_before
+        n_out = sp.tokens_out.numel()
+        state = host[n_out:n_out + sampling.SPEC_STATE_WORDS].tolist()
+        self.gen_stats.update(spec_rounds=state[sampling.SPEC_ROUNDS], spec_drafted=state[sampling.SPEC_DRAFTED], spec_accepted=state[sampling.SPEC_ACCEPTED])
+        if state[sampling.SPEC_INVALID] or int(host[-1]):
+            raise RuntimeError("generate: the sequence produced an invalid token (NaN / Inf logits)")
+        new = host[:state[sampling.SPEC_PRODUCED]].long()
+        if stop is not None and self.gen_stats["stopped_after"] is None and state[sampling.SPEC_DONE]:
+            self.gen_stats["stopped_after"] = self.gen_stats["graph_replays"]
+        if eos_token_id is not None:
+            hit = (new == eos_token_id).nonzero().flatten()
+            if hit.numel():
+                new = new[:int(hit[0]) + 1]
+        return new if one else new.unsqueeze(0)
 
     #: tensor-parallel ranks take the fx pipeline too (round 4): 7 launches per layer instead of the glue pipeline's 8-10
     fx_under_tp = os.environ.get("EXL3_HIP_FX_UNDER_TP", "1") != "0"

@@ -284,3 +284,90 @@ def process_logits(logits: torch.Tensor, procs: LogitProcessors, past_a: torch.T
                                          _p(bias), _p(bm), 0 if bm is None else bm.shape[0], 0 if bm is None else bm.shape[1],
                                          torch.cuda.current_stream(logits.device).cuda_stream))
     return out
+
+
+# ---- speculative decoding (csrc/exl3_spec.hip) -------------------------------------------------------------------------------------------------------------
+SPEC_BASE, SPEC_PRODUCED, SPEC_LIVE, SPEC_DONE, SPEC_INVALID, SPEC_NDRAFT, SPEC_ROUNDS, SPEC_DRAFTED, SPEC_ACCEPTED = range(9)
+SPEC_STATE_WORDS = 9           # include/exl3_hip.h EXL3_SPEC_STATE_WORDS
+SPEC_MAX_MATCH = 16
+
+
+@dataclass(frozen=True)
+class SpeculativeSettings:
+    """Speculative decoding in generate(): num_draft_tokens drafts per verify step (the step runs num_draft_tokens + 1 rows, so at most 15).  The drafts come
+    from the n-gram matcher over the sequence's own history (the longest suffix of ngram_match_min .. ngram_match_max tokens that occurred before, continued
+    the way it continued then) or, with script (token ids by ABSOLUTE position, -1 = no draft from here; shorter than the context: padded with -1), from that
+    table -- the seam for a host-side or draft-model drafter, and how tests force acceptance patterns.  The drafts never change the output, only the number
+    of verify steps it takes.  The default of 3 drafts: m = 4 is the widest batch of the 1-4-row GEMV generation."""
+    num_draft_tokens: int = 3
+    ngram_match_min: int = 2
+    ngram_match_max: int = 8
+    script: object = None
+
+    def __post_init__(self):
+        k, lo, hi = int(self.num_draft_tokens), int(self.ngram_match_min), int(self.ngram_match_max)
+        if not (1 <= k <= MAX_ROWS - 1):
+            raise ValueError("SpeculativeSettings: num_draft_tokens must be in [1, 15]")
+        if not (1 <= lo <= hi <= SPEC_MAX_MATCH):
+            raise ValueError("SpeculativeSettings: 1 <= ngram_match_min <= ngram_match_max <= 16")
+
+
+def _spec_check(name, x0, embed, int_tensors, state, m):
+    ok = (x0.is_cuda and x0.dtype == torch.half and x0.dim() == 2 and x0.is_contiguous() and embed.dtype == torch.half and embed.dim() == 2 and embed.is_contiguous()
+          and embed.shape[1] == x0.shape[1] and embed.device == x0.device)
+    for t, n in int_tensors:
+        ok = ok and (t is None or (t.dtype == torch.int32 and t.is_contiguous() and t.device == x0.device and t.numel() >= n))
+    ok = ok and state.numel() >= SPEC_STATE_WORDS and 1 <= m <= MAX_ROWS
+    if not ok:
+        raise RuntimeError(f"{name}: fp16 embed [vocab, hidden] / x0 [m, hidden] (m <= 16), contiguous int32 tensors on the device of x0, a state of {SPEC_STATE_WORDS} words")
+    if x0.device.index != torch.cuda.current_device():
+        torch.cuda.set_device(x0.device)
+
+
+def spec_accept(sampled: torch.Tensor, in_tokens: torch.Tensor, state: torch.Tensor, round_word: torch.Tensor, hist: torch.Tensor, tokens_out: torch.Tensor,
+                vocab: int, stop_ids: torch.Tensor | None = None, max_new: int | None = None):
+    """exl3_spec_accept: the launch behind the sampler of a verify step -- commits the drafts that equal the target's own tokens and the one token behind them
+    (sampled[0 .. n] -> hist and tokens_out), advances base / produced / round and the counters in `state` (int32 [SPEC_STATE_WORDS]); max_new defaults
+    to tokens_out.numel().  Stop ids, the budget and an out-of-vocabulary sample cut the run (include/exl3_hip.h)."""
+    m = in_tokens.numel()
+    ok = all(t.dtype == torch.int32 and t.is_contiguous() and t.is_cuda and t.device == state.device for t in (sampled, in_tokens, state, hist, tokens_out))
+    ok = ok and (stop_ids is None or (stop_ids.dtype == torch.int32 and stop_ids.is_contiguous() and stop_ids.device == state.device))
+    max_new = tokens_out.numel() if max_new is None else int(max_new)
+    ok = ok and sampled.numel() >= m and 0 <= max_new <= tokens_out.numel() and state.numel() >= SPEC_STATE_WORDS and round_word.dtype == torch.int64 and round_word.numel() == 1 and round_word.device == state.device
+    if not ok:
+        raise RuntimeError("spec_accept: contiguous int32 sampled / in_tokens [m] / state / hist / tokens_out / stop_ids and an int64 round word on one GPU")
+    if state.device.index != torch.cuda.current_device():
+        torch.cuda.set_device(state.device)
+    _check(_lib.lib().exl3_spec_accept(_p(sampled), _p(in_tokens), m, int(vocab), _p(state), _p(round_word), _p(hist), hist.numel(), _p(tokens_out), max_new,
+                                       _p(stop_ids), 0 if stop_ids is None else stop_ids.numel(), torch.cuda.current_stream(state.device).cuda_stream))
+
+
+def spec_draft(hist: torch.Tensor, state: torch.Tensor, in_tokens: torch.Tensor, embed: torch.Tensor, x0: torch.Tensor, positions: torch.Tensor,
+               cache_seqlens: torch.Tensor, attn_lens: torch.Tensor, k: int, max_new: int, match_min: int = 2, match_max: int = 8,
+               script: torch.Tensor | None = None, vocab: int | None = None):
+    """exl3_spec_draft_ngram: up to k drafts behind the committed history hist[0 .. base] (n-gram match, or script[base + 1 ..] when a script is given) and the
+    inputs of the next verify step: in_tokens [m], state's n_draft, positions / cache_seqlens / attn_lens [m] and x0 [m, hidden] = embed[in_tokens]."""
+    m = x0.shape[0]
+    _spec_check("spec_draft", x0, embed, ((hist, 1), (state, SPEC_STATE_WORDS), (in_tokens, m), (positions, m), (cache_seqlens, m), (attn_lens, m), (script, hist.numel())),
+                state, m)
+    _check(_lib.lib().exl3_spec_draft_ngram(_p(hist), hist.numel(), _p(script), int(k), int(match_min), int(match_max), m, _p(state), int(max_new), _p(in_tokens),
+                                            _p(embed), int(embed.shape[0] if vocab is None else vocab), x0.shape[1], _p(x0), _p(positions), _p(cache_seqlens),
+                                            _p(attn_lens), torch.cuda.current_stream(x0.device).cuda_stream))
+
+
+def spec_round(sampled: torch.Tensor, in_tokens: torch.Tensor, state: torch.Tensor, round_word: torch.Tensor, hist: torch.Tensor, tokens_out: torch.Tensor,
+               embed: torch.Tensor, x0: torch.Tensor, positions: torch.Tensor, cache_seqlens: torch.Tensor, attn_lens: torch.Tensor, k: int, match_min: int = 2,
+               match_max: int = 8, script: torch.Tensor | None = None, stop_ids: torch.Tensor | None = None, vocab: int | None = None, max_new: int | None = None):
+    """exl3_spec_round: spec_accept followed by spec_draft in ONE launch (max_new defaults to tokens_out.numel())."""
+    m = x0.shape[0]
+    max_new = tokens_out.numel() if max_new is None else int(max_new)
+    if not (0 <= max_new <= tokens_out.numel()):
+        raise RuntimeError("spec_round: max_new outside tokens_out")
+    _spec_check("spec_round", x0, embed, ((sampled, m), (hist, 1), (state, SPEC_STATE_WORDS), (in_tokens, m), (tokens_out, 0), (positions, m), (cache_seqlens, m),
+                                          (attn_lens, m), (script, hist.numel()), (stop_ids, 0)), state, m)
+    if not (round_word.dtype == torch.int64 and round_word.numel() == 1 and round_word.device == x0.device):
+        raise RuntimeError("spec_round: the round word must be one int64 word on the device of x0")
+    _check(_lib.lib().exl3_spec_round(_p(sampled), _p(in_tokens), m, int(embed.shape[0] if vocab is None else vocab), _p(state), _p(round_word), _p(hist), hist.numel(),
+                                      _p(tokens_out), max_new, _p(stop_ids), 0 if stop_ids is None else stop_ids.numel(), _p(script), int(k),
+                                      int(match_min), int(match_max), _p(embed), x0.shape[1], _p(x0), _p(positions), _p(cache_seqlens), _p(attn_lens),
+                                      torch.cuda.current_stream(x0.device).cuda_stream))

@@ -795,6 +795,38 @@ int exl3_logit_process(const void* logits_in, int in_fp32, void* logits_out, int
                        float rep_p, int rep_sustain, int rep_decay, float pres_p, float freq_p, int pf_sustain, int pf_decay,
                        const float* bias, const uint32_t* bitmask, int bitmask_rows, int bitmask_words, void* stream);
 
+/* ---- speculative decoding between two verify steps (exl3_spec.hip)    generator/generator.py (num_draft_tokens), generator/job.py (get_ngram_draft; the
+ *      reference accepts and drafts on the host -- here both sit inside the replayed graph) ------------------------------------------------------------------
+ * A verify step runs m = k + 1 rows of ONE sequence: in_tokens[0] is the last committed token at position base, in_tokens[1 .. n_draft] are drafts, the rest is
+ * padding; row i's logits are the target's distribution for position base + i + 1 and sampled[i] is the sampler's token for that row.
+ * state: int32 words  [0] base  [1] produced  [2] live  [3] done (sticky)  [4] invalid (sticky)  [5] n_draft  [6] rounds_live  [7] drafted  [8] accepted
+ *   (EXL3_SPEC_STATE_WORDS of them).  round: a DEVICE int64 word (the sampler's step word).  hist: int32 [max_ctx], tokens by absolute position;
+ *   hist[0 .. base] is committed.  frozen = done or invalid or produced >= max_new.
+ * exl3_spec_accept: one launch behind the sampler, the only place state advances.  *round += 1 always.  Frozen: live = 0 and nothing else changes (surplus
+ *   replays are harmless).  Else n = the largest j <= n_draft with in_tokens[i] == sampled[i - 1] for all 1 <= i <= j, cut so that produced + n + 1 <= max_new;
+ *   for i = 0 .. n in order: sampled[i] -> hist[base + 1 + i] and tokens_out[produced + i]; a sampled[i] outside [0, vocab) (or a position outside hist) is not
+ *   emitted, sets invalid and ends the run; an emitted token that is one of stop_ids (n_stop <= 64) is kept, sets done and ends the run.  With e tokens emitted:
+ *   base += e, produced += e, rounds_live += 1, drafted += n_draft, accepted += max(e - 1, 0), live = !frozen.
+ * exl3_spec_draft_ngram: the drafter and the feed of the next verify step, one launch.  Frozen: changes nothing.  L = base + 1.
+ *   script == NULL (n-gram): the longest n in [match_min, match_max] (match_max <= 16) for which hist[L - n .. L) == hist[e - n .. e) for some n <= e <= L - 1;
+ *   among the matches of that n the largest e; the draft is hist[e .. e + c), c = min(k, L - e); no match: c = 0.
+ *   script != NULL (int32 [max_ctx] by absolute position, the seam for a host-side or draft-model drafter): the draft is script[L .. L + c), c = the count of
+ *   leading entries inside [0, vocab), at most k (-1 = no draft from here).
+ *   Feed: in_tokens[0] = hist[base], in_tokens[i] = draft i for i <= c, = in_tokens[0] for c < i < m (padding: a valid id); n_draft = c;
+ *   positions[i] = cache_seqlens[i] = base + i, attn_lens[i] = base + i + 1, x0[i] = embed[in_tokens[i]] (fp16, 16-byte copies) for all m rows.  k <= m - 1.
+ *   A base with base + m - 1 >= max_ctx (a row would append outside the cache) feeds nothing and sets invalid.
+ * exl3_spec_round: exl3_spec_accept followed by exl3_spec_draft_ngram in ONE launch (one workgroup: a barrier orders the accept's writes before the scan).
+ * All three: one workgroup, graph-capturable, allocate nothing, no workspace; no workgroup waits for another. */
+#define EXL3_SPEC_STATE_WORDS 9
+int exl3_spec_accept(const int32_t* sampled, const int32_t* in_tokens, int m, int vocab, int32_t* state, int64_t* round, int32_t* hist, int max_ctx,
+                     int32_t* tokens_out, int max_new, const int32_t* stop_ids, int n_stop, void* stream);
+int exl3_spec_draft_ngram(const int32_t* hist, int max_ctx, const int32_t* script, int k, int match_min, int match_max, int m, int32_t* state, int max_new,
+                          int32_t* in_tokens, const void* embed, int vocab, int hidden, void* x0, int32_t* positions, int32_t* cache_seqlens,
+                          int32_t* attn_lens, void* stream);
+int exl3_spec_round(const int32_t* sampled, int32_t* in_tokens, int m, int vocab, int32_t* state, int64_t* round, int32_t* hist, int max_ctx,
+                    int32_t* tokens_out, int max_new, const int32_t* stop_ids, int n_stop, const int32_t* script, int k, int match_min, int match_max,
+                    const void* embed, int hidden, void* x0, int32_t* positions, int32_t* cache_seqlens, int32_t* attn_lens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

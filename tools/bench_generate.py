@@ -18,6 +18,12 @@
             (SyntheticEXL3Llama.gen_prefill_chunk) is taken; and the same ingestion with dequant_cache_paged switched off (timing only: the share of
             re-expanding the past for every chunk and layer).
 
+  speculative  generate(speculative=...) (written to profiles/spec_decode_bench.json): the replayed body (m-row fused verify step + sampler + accept / draft / feed)
+            at m = 1 against the plain replayed loop (the price of leaving the persistent step) and at m = 2, 3, 4, 5, 8; tokens/s with an oracle script (every
+            draft accepted: the ceiling), an all-wrong script (the floor: pure overhead) and the n-gram drafter on the model's own greedy output with its
+            acceptance; the break-even acceptance per m; accept + draft as one launch against two; the share of the decode attention in the m-row step at
+            1000 and 16 000 cached tokens (every row re-reads the quantized K / V).
+
 Method: device events around whole windows that end in a synchronise, every shape warmed up, windows of at least --window seconds, the two sides of a comparison
 alternating in one process, min / median / max of the repeated windows reported.  A run without a GPU fails."""
 import argparse
@@ -321,13 +327,165 @@ def bench_prompt(dev, args, shape_name):
     return out
 
 
+def bench_speculative(dev, args, shape_name):
+    import copy
+    import torch
+    from exllamav3_amd import sampling
+    from exllamav3_amd.llama_path import SHAPES, SyntheticEXL3Llama
+    m = SyntheticEXL3Llama(SHAPES[shape_name], K=4, cb=2, device=dev, kv_bits=4, layers=args.layers or None)
+    ctx = m.max_ctx
+    m.with_attention = True
+    prompt = torch.tensor([128000, 9906, 11, 856, 836, 374, 1234, 77])
+    P, new = prompt.numel(), args.new_tokens
+    ka = sampling.SamplerSettings(temperature=0.0).kernel_args()
+    out = {"shape": shape_name, "layers": m.n_layers, "prompt_tokens": P, "new_tokens": new, "max_ctx": ctx}
+    # the plain loop: prompt ingested, then `new` replays of gen_step (persistent step where it applies)
+    gs = m.alloc_gen_state(1, new, prompt.view(1, -1))
+    m.gen_step(ka); torch.cuda.synchronize()
+    out["persistent_step"] = bool(m._pstep is not None and not m._pstep.error())
+    m._gen_prime_prefilled()
+    g_plain = graph_of(lambda: m.gen_step(ka), 1)
+
+    def plain_loop():
+        # _gen_prime_prefilled without the ingestion (the prompt's K / V stay where the first call put them, as they do on the speculative side)
+        m._gen_prime()
+        m.positions.fill_(P - 2); m.cache_seqlens.fill_(P - 2); m.attn_lens.fill_(P - 1)
+        gs.step.fill_(P - 2)
+        gs.tokens_out[:, :P - 2] = gs.forced[:, 1:P - 1]
+        sampling.gen_feed(None, gs.forced, gs.embed, m.x0, gs.tokens_out, m.positions, m.cache_seqlens, m.attn_lens, gs.invalid, gs.step, vocab=m.shape.vocab)
+        for _ in range(new):
+            g_plain.replay()
+
+    sides = {"plain_generate": (plain_loop, new)}
+    info = {}
+    for rows in (1, 2, 3, 4, 5, 8):
+        k = rows - 1
+        mm = copy.copy(m)                                                 # the weights shared, a state of its own
+        mm.spec_fold = True
+        script = torch.full((ctx,), -1, dtype=torch.int32, device=dev)
+        sp = mm.alloc_spec_state(k, new, prompt, sampling.SpeculativeSettings(script=script.cpu()))
+        mm._spec_ingest(); mm._spec_prime()
+        mm.spec_step(ka); torch.cuda.synchronize()
+        mm._spec_prime()
+        g_script = graph_of(lambda mm=mm: mm.spec_step(ka), 1)
+        mm._spec_prime()
+
+        def loop(mm=mm, g=g_script, n=new):
+            mm._spec_prime()
+            for _ in range(n):
+                g.replay()
+
+        loop(); torch.cuda.synchronize()                                  # no drafts: one token per round = this m's own greedy continuation
+        truth = mm.spec.tokens_out[:new].clone()
+        assert int(mm.spec.state[sampling.SPEC_PRODUCED]) == new and not int(mm.spec.state[sampling.SPEC_INVALID])
+        oracle, wrong = script.clone(), script.clone()
+        oracle[P:P + new] = truth
+        wrong[P:P + new] = (truth + 1) % m.shape.vocab
+
+        def scripted(table, n, mm=mm, g=g_script):
+            mm.spec.script.copy_(table)
+            mm._spec_prime()
+            for _ in range(n):
+                g.replay()
+
+        r_oracle = math.ceil(new / rows)
+        scripted(oracle, r_oracle); torch.cuda.synchronize()
+        assert int(mm.spec.state[sampling.SPEC_PRODUCED]) == new and torch.equal(mm.spec.tokens_out[:new], truth), "the oracle script changed the tokens"
+        sides[f"m{rows}_body_all_wrong_script"] = (lambda wrong=wrong, scripted=scripted: scripted(wrong, new), new)
+        info[rows] = {"rounds_oracle": r_oracle}
+        if k >= 1:
+            sides[f"m{rows}_oracle_script"] = (lambda oracle=oracle, scripted=scripted, r=r_oracle: scripted(oracle, r), new)
+            ng = copy.copy(m)
+            ng.spec_fold = True
+            ng.alloc_spec_state(k, new, prompt, sampling.SpeculativeSettings(num_draft_tokens=k))
+            ng._spec_ingest(); ng._spec_prime()
+            ng.spec_step(ka); torch.cuda.synchronize()
+            ng._spec_prime()
+            g_ng = graph_of(lambda ng=ng: ng.spec_step(ka), 1)
+            ng._spec_prime()
+            rounds = 0
+            while int(ng.spec.live.cpu()):
+                g_ng.replay(); rounds += 1
+            st = ng.spec.state.tolist()
+            assert st[sampling.SPEC_PRODUCED] == new and torch.equal(ng.spec.tokens_out[:new], truth), "the n-gram drafter changed the tokens"
+            info[rows].update(rounds_ngram=rounds, ngram_drafted=st[sampling.SPEC_DRAFTED], ngram_accepted=st[sampling.SPEC_ACCEPTED],
+                              ngram_acceptance=round(st[sampling.SPEC_ACCEPTED] / max(st[sampling.SPEC_DRAFTED], 1), 4),
+                              ngram_tokens_per_round=round(new / rounds, 3))
+
+            def ng_loop(ng=ng, g=g_ng, n=rounds):
+                ng._spec_prime()
+                for _ in range(n):
+                    g.replay()
+
+            sides[f"m{rows}_ngram"] = (ng_loop, new)
+        if rows == 4:
+            tw = copy.copy(m)
+            tw.spec_fold = False
+            tw.alloc_spec_state(k, new, prompt, sampling.SpeculativeSettings(script=wrong.cpu()))
+            tw._spec_ingest(); tw._spec_prime()
+            tw.spec_step(ka); torch.cuda.synchronize()
+            tw._spec_prime()
+            g_tw = graph_of(lambda tw=tw: tw.spec_step(ka), 1)
+
+            def tw_loop(tw=tw, g=g_tw):
+                tw._spec_prime()
+                for _ in range(new):
+                    g.replay()
+
+            sides["m4_body_all_wrong_script_two_launches"] = (tw_loop, new)
+    r = alternate(sides, args.window, args.repeats)
+    plain = r["plain_generate"]["median"]
+    out["plain_generate"] = dict(r["plain_generate"], unit="us per token", tokens_per_s=round(1e6 / plain, 1))
+    for rows, inf in info.items():
+        body = r[f"m{rows}_body_all_wrong_script"]
+        e = dict(inf, body_us_per_replay=body, floor_tokens_per_s=round(1e6 / body["median"], 1), body_over_plain=round(body["median"] / plain, 4))
+        if rows > 1:
+            # the round costs body / plain plain-steps and yields 1 + a (rows - 1) tokens at per-draft acceptance a (drafts always full): break-even a
+            e["break_even_tokens_per_round"] = round(body["median"] / plain, 4)
+            e["break_even_acceptance_per_draft"] = round((body["median"] / plain - 1.0) / (rows - 1), 4)
+            o, n = r[f"m{rows}_oracle_script"], r[f"m{rows}_ngram"]
+            e["ceiling_oracle_script"] = dict(o, unit="us per token", tokens_per_s=round(1e6 / o["median"], 1))
+            e["ngram"] = dict(n, unit="us per token", tokens_per_s=round(1e6 / n["median"], 1))
+        out[f"m{rows}"] = e
+    out["m4_two_launches_body_us_per_replay"] = r["m4_body_all_wrong_script_two_launches"]
+    print("speculative", shape_name, json.dumps(out), flush=True)
+    # the decode attention's share of the m-row fused step at long contexts: rows of ONE sequence, each re-reading the quantized K / V up to its own length
+    att = {}
+    for pos in (1000, 16000):
+        s2 = {}
+        for rows in (1, 4, 8):
+            for on in (True, False):
+                mm = copy.copy(m)
+                mm.with_attention = on
+                mm.max_ctx = 16384 + 512                                   # (only allocation reads it)
+                mm._alloc_state(rows, pos, None, one_sequence=True)
+                ar = torch.arange(rows, dtype=torch.int32, device=dev)
+                mm.positions.copy_(pos + ar); mm.cache_seqlens.copy_(pos + ar); mm.attn_lens.copy_(pos + 1 + ar)
+                mm.attn_pos = pos + rows
+                mm.attn_ws = torch.empty((rows * mm.hq * ((pos + rows + 32) // 32) * 132,), dtype=torch.float, device=dev)
+                g = graph_of(mm.decode_step_fused, 1)
+                s2[f"m{rows}_{'attention' if on else 'no_attention'}"] = (lambda g=g, keep=mm: g.replay(), 1)
+        r2 = alternate(s2, args.window / 2, args.repeats)
+        e = {}
+        for rows in (1, 4, 8):
+            a, b = r2[f"m{rows}_attention"]["median"], r2[f"m{rows}_no_attention"]["median"]
+            e[f"m{rows}"] = {"step_us": a, "step_without_attention_us": b, "attention_share": round(1.0 - b / a, 4)}
+        att[str(pos)] = e
+        print("speculative attention share", shape_name, pos, json.dumps(e), flush=True)
+    out["attention_share_of_fused_step"] = att
+    del m, sides
+    torch.cuda.empty_cache()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--window", type=float, default=1.0, help="seconds per timed window (at least)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--new-tokens", type=int, default=256)
     ap.add_argument("--layers", type=int, default=0, help="debug: fewer layers (invalidates the number)")
-    ap.add_argument("--skip", default="", help="comma list of: sampler, 8b, 1b, processors, prompt (a skipped section keeps what --out already holds)")
+    ap.add_argument("--skip", default="", help="comma list of: sampler, 8b, 1b, processors, prompt, speculative (a skipped section keeps what --out already holds)")
+    ap.add_argument("--spec-out", default=os.path.join(ROOT, "profiles", "spec_decode_bench.json"), help="section speculative: its own result file")
     ap.add_argument("--prompt-lengths", default="8,64,512,2048,8192", help="section prompt: prompt lengths")
     ap.add_argument("--prompt-chunks", default="512,1024,2048,4096", help="section prompt: the chunk sweep of ingest_prompt")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "generate_bench.json"))
@@ -357,10 +515,18 @@ def main():
         res["generate_processors"] = {shape: bench_generate_processors(dev, args, shape) for shape in ("llama-3.1-8b", "llama-3.2-1b")}
     if "prompt" not in skip:
         res["prompt"] = {shape: bench_prompt(dev, args, shape) for shape in ("llama-3.1-8b", "llama-3.2-1b")}
-    os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "w") as f:
-        json.dump(res, f, indent=1)
-    print("wrote", args.out)
+    if "speculative" not in skip:
+        spec = {"device": res["device"], "method": res["method"], "when": res["when"],
+                "speculative": {shape: bench_speculative(dev, args, shape) for shape in ("llama-3.1-8b", "llama-3.2-1b")}}
+        os.makedirs(os.path.dirname(args.spec_out), exist_ok=True)
+        with open(args.spec_out, "w") as f:
+            json.dump(spec, f, indent=1)
+        print("wrote", args.spec_out)
+    if not {"sampler", "8b", "1b", "processors", "prompt"} <= skip:
+        os.makedirs(os.path.dirname(args.out), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("wrote", args.out)
 
 
 if __name__ == "__main__":
