@@ -85,44 +85,72 @@ bool plan_op(int ncu, int nblk, const int* ncb, int nmat, int in_type, int out_t
 // How the twelve streaming waves share a rectangle of T = 4 nb x ncb work units (H = 4 nb per column).  A SIMD hosts waves w, w + 4, w + 8 and arbitrates oldest-first: the
 // age groups A (0-3) / B (4-7) / C (8-11) stream at ~ 1.05 / 0.89 / 0.44 units per us while all three run (per-unit stamps of an 8B gate|up op: profiles/r06_*), so equal runs
 // leave the youngest wave streaming alone, latency-bound, for the last third of the phase.  Every wave decodes `pre` units ahead while the op's input is on its way (those cost
-// no time behind the input); the REST of the SIMD's share is cut in the ratio of the groups' rates (permille fA : fB : 1000 - fA - fB).  out[g] = n_g << 2 | e_g: the four waves
-// of group g take n_g units, the first e_g of them one more.  All zero = the uniform partition [T w / 12, T (w + 1) / 12): rectangles whose units are all decoded ahead, runs
-// that would be longer than a column (a wave keeps two partial rows: its run may cross ONE column boundary), and the lm_head (its finish still uses the closed formulas).
+// no time behind the input); the REST of the SIMD's share is cut in the ratio of the groups' rates (permille fA : fB : 1000 - fA - fB).
+// The cut is made in WHOLE SIMD ROWS: the phase is VALU-bound per SIMD and ends when the fullest SIMD ends, so every SIMD gets the same a + b + c = T / 4 units (T is a
+// multiple of 4), the integers a >= b >= c nearest to pre + rest f_g / 1000.  (A group total rounded freely hands its remainder to the group's FIRST waves, and the first waves
+// of all three groups -- 0 / 4 / 8 -- are one SIMD: 8B gate|up was 29 / 28 / 28 / 27 units per SIMD, down 15 / 14 / 14 / 13.)  out[g] = n_g << 2 | e_g: the four waves of group
+// g take n_g units, the first e_g of them one more (ps_wave_range); this planner always emits e_g = 0.  All zero = the uniform partition [T w / 12, T (w + 1) / 12): rectangles
+// whose units are all decoded ahead, and cuts that no triple near the shares can make (below).  The lm_head's rectangles are cut like any other (their partial rows take the
+// service-wave sum).
+// A triple is refused when the youngest group would keep less than it decodes ahead, when it is not ordered a >= b >= c with a > c (a = c is the uniform cut), when a run would
+// be longer than a column (a wave keeps two partial rows: its run may cross ONE column boundary), or when a column's partial rows would come from more than eight
+// consecutive waves; the triples are tried nearest first, so a refusal of the nearest moves the cut to a neighbour instead of turning the weighting off.
+bool wave_triple_ok(int T, int H, int pre, const int* n)
+{
+    if (n[2] < pre || n[0] < n[1] || n[1] < n[2] || n[0] == n[2] || n[0] > H) return false;
+    // the finish reads the partial rows of a column from at most EIGHT consecutive waves (exl3_pstep_kernel.cuh: col_table): check every column of this cut
+    int u0[12], u1[12], b = 0;
+    for (int g = 0; g < 3; ++g) for (int i = 0; i < 4; ++i) { u0[4 * g + i] = b; b += n[g]; u1[4 * g + i] = b; }
+    for (int j = 0; j * H < T; ++j)
+    {
+        int first = -1, last = -1;
+        for (int w = 0; w < 12; ++w) if (u0[w] < (j + 1) * H && u1[w] > j * H) { if (first < 0) first = w; last = w; }
+        if (first >= 0 && last - first >= 8) return false;
+    }
+    return true;
+}
+
 void wave_partition(int T, int H, int pre, int fA, int fB, int* out)
 {
     out[0] = out[1] = out[2] = 0;
-    if (fA <= 0 || fB <= 0 || fA + fB >= 1000 || T <= 12 * pre) return;
-    const double rest = (double) T / 4.0 - 3.0 * pre;                        // units per SIMD streamed behind the input
-    int G[3];
-    G[0] = (int) (4.0 * (pre + rest * fA / 1000.0) + 0.5);
-    G[1] = (int) (4.0 * (pre + rest * fB / 1000.0) + 0.5);
-    G[2] = T - G[0] - G[1];
-    if (G[2] < 4 * pre || G[0] < G[1] || G[1] < G[2]) return;
-    for (int g = 0; g < 3; ++g) if ((G[g] + 3) / 4 > H) return;             // (a run longer than a column would cross two boundaries)
-    // the finish reads the partial rows of a column from at most EIGHT consecutive waves (exl3_pstep_kernel.cuh: col_table): check every column of this cut
-    {
-        int u0[12], u1[12], b = 0;
-        for (int g = 0; g < 3; ++g) { const int n = G[g] / 4, e = G[g] % 4; for (int i = 0; i < 4; ++i) { u0[4 * g + i] = b + i * n + (i < e ? i : e); u1[4 * g + i] = u0[4 * g + i] + n + (i < e ? 1 : 0); } b += G[g]; }
-        for (int j = 0; j * H < T; ++j)
+    if (fA <= 0 || fB <= 0 || fA + fB >= 1000 || T <= 12 * pre || (T & 3)) return;
+    const int q = T / 4, rest = q - 3 * pre;                                 // units per SIMD; those streamed behind the input
+    const long long tA = 1000LL * pre + (long long) rest * fA, tB = 1000LL * pre + (long long) rest * fB, tC = 1000LL * q - tA - tB;      // the groups' targets, in 1/1000 unit
+    // candidates around the targets, nearest (least squares) first; ties: the older group takes more
+    struct Cand { long long d; int n[3]; };
+    Cand cand[64]; int nc = 0;
+    for (int a = (int) (tA / 1000) + 3; a >= (int) (tA / 1000) - 2; --a)
+        for (int b = (int) (tB / 1000) + 3; b >= (int) (tB / 1000) - 2; --b)
         {
-            int first = -1, last = -1;
-            for (int w = 0; w < 12; ++w) if (u1[w] > u0[w] && u0[w] < (j + 1) * H && u1[w] > j * H) { if (first < 0) first = w; last = w; }
-            if (first >= 0 && last - first >= 8) return;
+            const int c = q - a - b;
+            const long long da = 1000LL * a - tA, db = 1000LL * b - tB, dc = 1000LL * c - tC;
+            Cand k; k.d = da * da + db * db + dc * dc; k.n[0] = a; k.n[1] = b; k.n[2] = c;
+            int i = nc++;
+            for (; i > 0 && cand[i - 1].d > k.d; --i) cand[i] = cand[i - 1];
+            cand[i] = k;
         }
-    }
-    for (int g = 0; g < 3; ++g) out[g] = ((G[g] / 4) << 2) | (G[g] % 4);
+    for (int i = 0; i < nc; ++i)
+        if (wave_triple_ok(T, H, pre, cand[i].n)) { for (int g = 0; g < 3; ++g) out[g] = cand[i].n[g] << 2; return; }
 }
 
-// the shares of the age groups (permille of the units streamed behind the input): EXL3_HIP_PSTEP_SHARES="fA,fB" overrides ("0,0": uniform partition everywhere)
-void wave_shares(int& fA, int& fB)
+// the shares of the age groups (permille of the units streamed behind the input), per op kind: the lm_head (purely VALU-bound, > 100 units per SIMD), down_proj (a few units
+// per SIMD behind the input: latency-dominated) and everything else (gate|up, where the shares were swept first).  Swept per kind on the whole-row cut, same box, Llama-3.1-8B
+// (profiles/pstep_simd_rows_sweep.txt): gate|up 474 : 421 : 105 = (12, 11, 5) units per wave, -1.9 % of the step against 460 : 370 : 170 = (12, 10, 6); down and the lm_head
+// did not move beyond the run-to-run spread and keep 460 : 370 : 170 (profiles/r06_pstep_wave_shares_ab.txt).  EXL3_HIP_PSTEP_SHARES="fA,fB" overrides all kinds ("0,0":
+// uniform partition everywhere), EXL3_HIP_PSTEP_SHARES_DOWN / EXL3_HIP_PSTEP_SHARES_HEAD one kind each (they win over the general one)
+enum { PS_SHARES_MAIN = 0, PS_SHARES_DOWN = 1, PS_SHARES_HEAD = 2 };
+void wave_shares(int kind, int& fA, int& fB)
 {
-    fA = 460; fB = 370;                    // (same-box sweep on MI355X, Llama-3.1-8B: profiles/r06_pstep_wave_shares_ab.txt)
-    if (const char* e = getenv("EXL3_HIP_PSTEP_SHARES")) { int a = 0, b = 0; if (sscanf(e, "%d,%d", &a, &b) == 2) { fA = a; fB = b; } }
+    if (kind == PS_SHARES_MAIN) { fA = 474; fB = 421; } else { fA = 460; fB = 370; }
+    auto take = [&] (const char* name) { if (const char* e = getenv(name)) { int a = 0, b = 0; if (sscanf(e, "%d,%d", &a, &b) == 2) { fA = a; fB = b; } } };
+    take("EXL3_HIP_PSTEP_SHARES");
+    if (kind == PS_SHARES_DOWN) take("EXL3_HIP_PSTEP_SHARES_DOWN");
+    if (kind == PS_SHARES_HEAD) take("EXL3_HIP_PSTEP_SHARES_HEAD");
 }
 
 // the rectangles of one op: workgroup (column group gi, slice s) = gi * S + s; every (column block, Hadamard block) of the op lies in exactly one
 // rectangle (tests/test_pstep_plan.py checks the partition on the CPU through exl3_pstep_plan_tiles)
-void fill_tiles(PsTile* T, int ncu, const OpPlan& p, const int* ncb, int nmat, int nblk, int side_tasks, bool weighted = true, int pre = 3)
+void fill_tiles(PsTile* T, int ncu, const OpPlan& p, const int* ncb, int nmat, int nblk, int side_tasks, bool weighted = true, int pre = 3, int shares_kind = PS_SHARES_MAIN)
 {
     for (int c = 0; c < ncu; ++c) { T[c].mat = -1; T[c].cb0 = 0; T[c].ncb = 0; T[c].b0 = 0; T[c].nb = 0; T[c].slice = 0; T[c].side = -1; T[c].flags = 0; T[c].ubase = 0; T[c].r0_ = T[c].r1_ = T[c].r2_ = 0; }
     int gi = 0;
@@ -144,7 +172,7 @@ void fill_tiles(PsTile* T, int ncu, const OpPlan& p, const int* ncb, int nmat, i
     int ub = 0;
     for (int c = 0; c < ncu; ++c) { T[c].ubase = ub; if (T[c].mat >= 0) ub += 4 * T[c].nb * T[c].ncb; }
     // the streaming waves' shares of every rectangle (wave_partition)
-    int fA, fB; wave_shares(fA, fB);
+    int fA, fB; wave_shares(shares_kind, fA, fB);
     for (int c = 0; c < ncu; ++c) if (weighted && T[c].mat >= 0)
     {
         int o3[3]; wave_partition(4 * T[c].nb * T[c].ncb, 4 * T[c].nb, pre, fA, fB, o3);
@@ -290,10 +318,10 @@ extern "C" int exl3_pstep_create(void** handle_out, const exl3_pstep_layer_t* la
     struct Pending { int op; int which; size_t off[PS_MAX_MATS]; int parity; };
     std::vector<Pending> slab_fix;
 
-    auto add_tiles = [&] (int op, const OpPlan& p, const int* ncb, int nmat, int nblk, int side_tasks)
+    auto add_tiles = [&] (int op, const OpPlan& p, const int* ncb, int nmat, int nblk, int side_tasks, int shares_kind = PS_SHARES_MAIN)
     {
         // (units every wave decodes ahead: the kernel's PM_MAIN / PM_2 -- three, two at 8 bits, for the wider of two widths when it is 6, and for 3INST / mcg)
-        fill_tiles(tiles.data() + (size_t) op * ncu, ncu, p, ncb, nmat, nblk, side_tasks, true, (cb_all != EXL3_CB_MUL1 || opK[(size_t) op] >= 8 || (K2 != K && opK[(size_t) op] == K2 && K2 >= 6)) ? 2 : 3);
+        fill_tiles(tiles.data() + (size_t) op * ncu, ncu, p, ncb, nmat, nblk, side_tasks, true, (cb_all != EXL3_CB_MUL1 || opK[(size_t) op] >= 8 || (K2 != K && opK[(size_t) op] == K2 && K2 >= 6)) ? 2 : 3, shares_kind);
     };
 
     int op = 0;
@@ -373,7 +401,7 @@ extern "C" int exl3_pstep_create(void** handle_out, const exl3_pstep_layer_t* la
             O.in_svh[0] = (const half_t*) L.gate.svh; O.in_svh[1] = (const half_t*) L.up.svh;
             const int ncb[1] = { hidden / 128 };
             OpPlan p; EXL3_CHECK_ARG(plan_op(ncu, inter / 128, ncb, 1, O.in_type, O.out_type, p, false, 32 / tpw), "exl3_pstep_create: no plan for down_proj");
-            O.S = p.S; add_tiles(op, p, ncb, 1, inter / 128, 0);
+            O.S = p.S; add_tiles(op, p, ncb, 1, inter / 128, 0, PS_SHARES_DOWN);
             O.rver = ++rver; O.gate_op = direct ? op - 1 : (rver >= 3 ? reader_of_version[rver - 2] : -1);
             { Pending f; f.op = op; f.which = 3; f.off[0] = 0; f.parity = PS_ROW_PARITY(li); slab_fix.push_back(f); const size_t n = (size_t) ncb[0] * p.S * tpw * 128; if (n > slab_d_floats) slab_d_floats = n; }
             if (li == 0) { snprintf(line, sizeof(line), "down: S=%d groups=%d tile<=%dx%d; ", p.S, p.g[0], p.wmax, p.hmax); desc += line; }
@@ -387,7 +415,7 @@ extern "C" int exl3_pstep_create(void** handle_out, const exl3_pstep_layer_t* la
         lin_to_mat(*head, O.mat[0]);
         const int ncb[1] = { head->n / 128 };
         OpPlan p; EXL3_CHECK_ARG(plan_op(ncu, hidden / 128, ncb, 1, O.in_type, O.out_type, p), "exl3_pstep_create: no plan for the lm_head (a rectangle is at most 12 column blocks wide: vocab / 128 <= 12 x CUs)");
-        O.S = p.S; fill_tiles(tiles.data() + (size_t) op * ncu, ncu, p, ncb, 1, hidden / 128, 0, true, (cb_all != EXL3_CB_MUL1 || KH != K || KH >= 8) ? 2 : 3);      // (units ahead: the kernel's head pass)
+        O.S = p.S; fill_tiles(tiles.data() + (size_t) op * ncu, ncu, p, ncb, 1, hidden / 128, 0, true, (cb_all != EXL3_CB_MUL1 || KH != K || KH >= 8) ? 2 : 3, PS_SHARES_HEAD);      // (units ahead: the kernel's head pass)
         snprintf(line, sizeof(line), "head: S=%d groups=%d tile<=%dx%d; residual edges: %s%s", p.S, p.g[0], p.wmax, p.hmax, direct ? "direct (consumer gathers)" : "owners", attn ? "; attention inside o_proj's preparation" : ""); desc += line;
         if (attn) { snprintf(line, sizeof(line), " (%d kv blocks x %d splits)", att_blocks, att_nsplit); desc += line; }
         ++op;
@@ -534,7 +562,7 @@ extern "C" int exl3_pstep_plan_tiles(int hidden, int inter, int heads_q, int hea
     }
     EXL3_CHECK_ARG(plan_op(ncu, nblk, ncb, nmat, in_type, out_type, p, direct), "exl3_pstep_plan_tiles: no plan for this op on %d CUs", ncu);
     std::vector<PsTile> T((size_t) ncu);
-    fill_tiles(T.data(), ncu, p, ncb, nmat, nblk, side, true);
+    fill_tiles(T.data(), ncu, p, ncb, nmat, nblk, side, true, 3, op_kind == 3 ? PS_SHARES_DOWN : op_kind == 4 ? PS_SHARES_HEAD : PS_SHARES_MAIN);
     memcpy(tiles_out, T.data(), (size_t) ncu * sizeof(PsTile));
     *S_out = p.S;
     return EXL3_OK;
