@@ -243,27 +243,38 @@ void routing_std_kernel(const half_t* __restrict__ hidden, const half_t* __restr
     __syncthreads();
     if (wave != 0) return;
 
-    // top-K by repeated arg-max over the wave (candidates e = lane + 64 j); ties go to the lower expert index
+    // top-K by repeated arg-max over the wave (candidates e = lane + 64 j); ties go to the lower expert index.  The logits are ranked through an
+    // order-preserving integer key (rank_key): +inf > finite > -inf > NaN, as the oracle's stable descending sort ranks them.  An untaken candidate
+    // always beats the start value (key 0, index 0x7fffffff), so every row -- a NaN hidden state, experts masked with a -inf bias, fp16 scores that
+    // overflowed -- gets K DISTINCT indices in [0, E): they index the pointer tables of the expert launches and per_expert_scale.  (Comparing the
+    // floats themselves, a NaN or a logit <= -1e30 was never accepted and the start index 0x7fffffff was written out.)
+    auto rank_key = [] (float v) -> uint32_t
+    {
+        if (v != v) return 0u;                             // NaN: below everything (-inf has key 0x007fffff)
+        const uint32_t b = __float_as_uint(v);
+        return (b & 0x80000000u) ? ((b << 1) ? ~b : 0x80000000u) : (b | 0x80000000u);    // -0.0 ranks with +0.0
+    };
     uint64_t taken_lo = 0;                                 // bit j: candidate j of this lane already selected (E <= 512 -> j < 8)
-    float max_logit = -1.0e30f;
+    float max_logit = 0.0f;
     for (int k = 0; k < K; ++k)
     {
-        float best = -1.0e30f; int best_e = 0x7fffffff;
+        uint32_t best = 0u; int best_e = 0x7fffffff;
         for (int j = 0; lane + 64 * j < E; ++j)
         {
             const int e = lane + 64 * j;
-            const float v = logit_s[e];
+            const uint32_t v = rank_key(logit_s[e]);
             if (!((taken_lo >> j) & 1) && (v > best || (v == best && e < best_e))) { best = v; best_e = e; }
         }
         #pragma unroll
         for (int i = 1; i < 64; i <<= 1)
         {
-            const float ov = xor_lane(best, i); const int oe = xor_lane(best_e, i);
+            const uint32_t ov = xor_lane(best, i); const int oe = xor_lane(best_e, i);
             if (ov > best || (ov == best && oe < best_e)) { best = ov; best_e = oe; }
         }
-        if (k == 0) max_logit = best;
+        const float best_v = logit_s[best_e];              // (K <= E: a candidate was left, best_e < E)
+        if (k == 0) max_logit = best_v;
         if ((best_e & 63) == lane) taken_lo |= 1ull << (best_e >> 6);
-        if (lane == 0) { sel_logit[k] = best; sel_idx[k] = best_e; }
+        if (lane == 0) { sel_logit[k] = best_v; sel_idx[k] = best_e; }
     }
     // softmax over the selected logits
     float ev = lane < K ? expf(sel_logit[lane] - max_logit) : 0.0f;

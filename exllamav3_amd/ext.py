@@ -515,13 +515,10 @@ def exl3_moe(hidden_state, output_state, expert_count, token_sorted, weight_sort
     # expert with more rows than m gets several slots, ns bounds their number.)
     _req(max_rows >= 1, "exl3_moe: temp_state_g must hold at least one row per expert (max_tokens_per_expert >= 1)")
     m = max(1, min(MOE_SLOT_ROWS, max_rows, T, bsz))
-    ns = min(E, T) + T // m
     dev = hidden_state.device
-    slot_expert = torch.empty((ns,), dtype=torch.long, device=dev)
-    slot_tok = torch.empty((ns * m,), dtype=torch.long, device=dev)
-    rowmap = torch.empty((T,), dtype=torch.int32, device=dev)
     st = _stream(hidden_state)
-    _check(_lib.lib().exl3_moe_build_slots(_p(expert_count), _p(token_sorted), E, T, max_rows, m, ns, _p(slot_expert), _p(slot_tok), _p(rowmap), st))
+    slot_expert, slot_tok, rowmap = moe_build_slots(expert_count[:E], token_sorted, max_rows, m)
+    ns = slot_expert.shape[0]
     A = hidden_state.index_select(0, slot_tok).view(ns, m, hidden)
     gated = act_function != MOE_ACT_RELU2_NOGATE
     U = torch.empty((ns, m, inter), dtype=torch.half, device=dev)
@@ -539,6 +536,27 @@ def exl3_moe(hidden_state, output_state, expert_count, token_sorted, weight_sort
         exl3_mgemm(Y, down_ptrs_trellis, D, down_ptrs_suh, None, down_ptrs_svh, slot_expert, None, K_down, -1, down_mcg, down_mul1, -1, -1, 0)
     # weighted scatter in a fixed order per token (bit-reproducible; the round-2 index_add_ was an atomic scatter)
     _check(_lib.lib().exl3_moe_scatter(_p(D), _p(rowmap), _p(token_sorted), _p(weight_sorted), _p(output_state), bsz, T, hidden, st))
+
+
+def moe_build_slots(expert_count: torch.Tensor, token_sorted: torch.Tensor, max_rows: int, m: int):
+    """The slot list of exl3_moe's indexed launches, built on the device (exl3_moe_build_slots): expert_count int64 [E], token_sorted int64 [T] (the
+    assignments grouped by expert), max_rows = the most rows an expert may have, m = rows per slot (1..16).  Returns (slot_expert int64 [ns],
+    slot_tok int64 [ns * m], rowmap int32 [T]) with ns = min(E, T) + T // m: slot j holds up to m consecutive assignments of ONE expert with
+    0 < count <= max_rows (rows past the chunk repeat its last assignment) or is unused (expert -1, tokens 0); rowmap[p] = j * m + r of assignment p,
+    -1 for assignments of refused experts."""
+    _dev(token_sorted)
+    _req(expert_count.dtype == torch.long and expert_count.dim() == 1 and expert_count.is_contiguous() and token_sorted.dtype == torch.long
+         and token_sorted.dim() == 1 and token_sorted.is_contiguous(), "moe_build_slots: expert_count / token_sorted must be contiguous 1-D int64")
+    E, T = int(expert_count.shape[0]), int(token_sorted.shape[0])
+    _req(E >= 1 and T >= 1 and int(max_rows) >= 1 and 1 <= int(m) <= MOE_SLOT_ROWS, "moe_build_slots: bad sizes")
+    ns = min(E, T) + T // int(m)
+    dev = token_sorted.device
+    slot_expert = torch.empty((ns,), dtype=torch.long, device=dev)
+    slot_tok = torch.empty((ns * int(m),), dtype=torch.long, device=dev)
+    rowmap = torch.empty((T,), dtype=torch.int32, device=dev)
+    _check(_lib.lib().exl3_moe_build_slots(_p(expert_count), _p(token_sorted), E, T, int(max_rows), int(m), ns, _p(slot_expert), _p(slot_tok), _p(rowmap),
+                                           _stream(token_sorted)))
+    return slot_expert, slot_tok, rowmap
 
 
 def moe_scatter(D: torch.Tensor, rowmap: torch.Tensor, token_sorted: torch.Tensor, weight_sorted: torch.Tensor, out: torch.Tensor):
@@ -1683,6 +1701,12 @@ class BC_MLP:
             self.down.run(u2, d.view(1, -1))
 
 
+def _req_router_bias(name: str, bias, experts: int, like: torch.Tensor):
+    """The router's optional logit bias: the launches read it as `experts` consecutive float16 values."""
+    _req(bias is None or (bias.dtype == torch.half and bias.is_contiguous() and bias.numel() == experts and bias.device == like.device),
+         f"{name}: bias must be a contiguous float16 tensor with one entry per expert, on the inputs' device")
+
+
 def routing_std(hidden, gate, scores, topk_indices, topk_weights, per_expert_scale=None, gate_t=None, bias=None, gu_slots=None):
     """routing.cu:955-1010 (same argument order): scores = hidden @ gate, top-K by logit, softmax over the selected logits.
     gu_slots (this build, optional): int64 [2][bsz * K] receiving [selected | selected + experts], the slot list of one indexed exl3_mgemm over
@@ -1695,6 +1719,7 @@ def routing_std(hidden, gate, scores, topk_indices, topk_weights, per_expert_sca
     _req(gate.dim() == 2 and gate.shape[0] == hidden.shape[-1] and gate.shape[1] == scores.shape[-1], "routing_std: gate must be (hidden, experts)")
     _req(topk_indices.shape == topk_weights.shape and scores.shape[0] == topk_indices.shape[0], "routing_std: shape mismatch")
     _req(hidden.is_contiguous() and gate.is_contiguous() and scores.is_contiguous(), "routing_std: tensors must be contiguous")
+    _req_router_bias("routing_std", bias, scores.shape[1], hidden)
     bsz = scores.shape[0]
     if gu_slots is not None:
         _req(gu_slots.dtype == torch.long and gu_slots.is_contiguous() and gu_slots.numel() == 2 * topk_indices.numel(), "routing_std: gu_slots must be int64 [2][bsz * K]")
@@ -1734,6 +1759,7 @@ def routing_std_norm(resid, norm_w, ss_part, eps: float, xn_out, gate, scores, t
          "routing_std_norm: resid, norm_w, xn_out, gate, scores must be float16")
     _req(ss_part.dtype == torch.float and topk_indices.dtype == torch.long and topk_weights.dtype == torch.half, "routing_std_norm: bad dtypes")
     _req(resid.is_contiguous() and xn_out.is_contiguous() and gate.is_contiguous() and scores.is_contiguous() and xn_out.shape == resid.shape, "routing_std_norm: bad layout")
+    _req_router_bias("routing_std_norm", bias, scores.shape[1], resid)
     bsz = scores.shape[0]
     _check(_lib.lib().exl3_routing_std_norm(_p(resid), _p(norm_w), _p(ss_part), float(eps), _p(xn_out), _p(gate), _p(bias), _p(scores), _p(topk_indices),
                                             _p(topk_weights), _p(gu_slots), bsz, resid.shape[-1], scores.shape[1], topk_indices.shape[1], _stream(resid)))
@@ -1748,6 +1774,7 @@ def routing_std_fx(resid_fx, norm_w, ss_out, eps: float, xn_out, gate, scores, t
     _req(ss_out.dtype == torch.float and topk_indices.dtype == torch.long and topk_weights.dtype == torch.half, "routing_std_fx: bad dtypes")
     _req(resid_fx.is_contiguous() and xn_out.is_contiguous() and gate.is_contiguous() and scores.is_contiguous() and xn_out.shape == resid_fx.shape
          and ss_out.is_contiguous() and ss_out.numel() >= resid_fx.numel() // 128, "routing_std_fx: bad layout")
+    _req_router_bias("routing_std_fx", bias, scores.shape[1], resid_fx)
     bsz = scores.shape[0]
     _check(_lib.lib().exl3_routing_std_fx(_p(resid_fx), _p(norm_w), _p(ss_out), float(eps), _p(xn_out), _p(gate), _p(bias), _p(scores), _p(topk_indices),
                                           _p(topk_weights), _p(gu_slots), bsz, resid_fx.shape[-1], scores.shape[1], topk_indices.shape[1], _stream(resid_fx)))

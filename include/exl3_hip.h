@@ -200,7 +200,10 @@ int exl3_mgemm_indexed(const void* A, int bszm_in, const void* tbl_B, const void
 
 /* routing_std(hidden, gate, scores, topk_indices, topk_weights, per_expert_scale, gate_t, bias)   routing.cu:955-1010, kernel :457-590
  * scores[bsz][E] fp16 = hidden[bsz][H] @ gate[H][E]; top-K logits (descending, ties to the lower index) -> topk_indices int64 [bsz][K],
- * topk_weights fp16 [bsz][K] = softmax over the K selected logits.  bias (fp16 [E], optional) is added to the logits before selection. */
+ * topk_weights fp16 [bsz][K] = softmax over the K selected logits.  bias (fp16 [E], optional) is added to the logits before selection.
+ * Non-finite logits (all router entry points): every row gets K DISTINCT indices in [0, E), ranked as a stable descending sort ranks the logits --
+ * +inf, finite values, -inf, then NaN, ties to the lower index (a row whose hidden state holds a NaN selects experts 0 .. K-1; experts masked with a
+ * -inf bias are selected only after every finite one).  The weights of a row whose selected logits are not all finite are unspecified. */
 int exl3_routing_std(const void* hidden, const void* gate, const void* bias, void* scores, int64_t* topk_indices, void* topk_weights,
                      int bsz, int hidden_size, int num_experts, int K, void* stream);
 
